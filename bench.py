@@ -14,16 +14,26 @@ Optional --rerank adds the cross-encoder top-100->10 pass (config 3);
 --rag adds a Phi-3-mini-shaped summarizer decode (config 5).
 
 Launch (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   # N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N
   #      --master-addr 127.0.0.1 bench.py --gpus N ...
 Scaling is WEAK: docs-per-GPU fixed, corpus grows with N; value is the
 whole-job queries/sec.
+
+A plain run does only what the headline figure needs: setup, warmup, the
+K timed steps, the JSON result line. --dump-outputs DIR additionally
+writes what the LAST timed step returned (fused / BM25 / dense hit ids +
+scores, rerank scores and summarizer tokens when those stages are on) as
+DIR/<name>.npy, so two builds can be compared output for output: all
+inputs are seeded, identical arguments give identical inputs. --full is
+where secondary measurements (anything that needs runs of its own)
+belong; today there are none, so it changes nothing.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import os
 import statistics
 import time
 
@@ -55,7 +65,35 @@ def parse_args():
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--phase-timers", action="store_true",
                    help="print per-phase time breakdown (adds syncs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as "
+                        "DIR/<name>.npy (float32 scores, float64 ids)")
+    p.add_argument("--full", action="store_true",
+                   help="also run secondary measurements beyond the "
+                        "headline figure (none exist today)")
     return p.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+NPY_HEADER_BYTES = 256      # upper bound of a .npy header for these arrays
+
+
+def dump_outputs(out_dir: str, arrays: dict, seed: int) -> None:
+    """Write each array as out_dir/<name>.npy (integers as float64, the
+    rest as float32). The files together, headers included, stay under
+    DUMP_BUDGET_BYTES: an array over its equal share is cut to a fixed
+    seeded sample of its flattened elements (ascending index order), the
+    same sample on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1) - NPY_HEADER_BYTES
+    for idx, (name, t) in enumerate(sorted(arrays.items())):
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype.kind in "iub" else np.float32)
+        cap = share // a.dtype.itemsize
+        if a.size > cap:
+            rng = np.random.default_rng(seed * 7919 + idx)
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -90,8 +128,9 @@ def main():
         from infomesh_amd.index.synth import synth_corpus_arrays
         terms, docs, lens = synth_corpus_arrays(
             docs_per_gpu, args.avg_doc_len, seed=args.seed * 1000 + rank)
+        g = torch.Generator().manual_seed(args.seed * 1000 + rank)
         emb = torch.nn.functional.normalize(
-            torch.randn(docs_per_gpu, 384), dim=-1).bfloat16()
+            torch.randn(docs_per_gpu, 384, generator=g), dim=-1).bfloat16()
         shard = CpuShard()
         gids = np.arange(docs_per_gpu, dtype=np.int64) * world + rank
         shard.build_from_arrays(terms, docs, lens, gids,
@@ -153,7 +192,8 @@ def main():
         lens = torch.full((B * n_cand,), 160, dtype=torch.int32,
                           device=device)
         scores = reranker.score_ids(ids, lens).view(B, n_cand)
-        torch.topk(scores, min(args.n_results, n_cand), dim=1)
+        top = torch.topk(scores, min(args.n_results, n_cand), dim=1)
+        return scores, top
 
     def run_rag():
         summarizer.reset()
@@ -179,8 +219,11 @@ def main():
             phase_t[name] = phase_t.get(name, 0.0) + (t1 - t0)
         return t1
 
-    def step(i: int) -> None:
+    def step(i: int) -> dict:
+        """One timed step; returns what a caller of the path receives
+        (rank 0 only, device tensors, not synchronized)."""
         j = i % n_batches
+        outs = {}
         emb = None
         encode_fn = None
         encode_shard = None
@@ -208,12 +251,21 @@ def main():
             if args.phase_timers else None, encode_fn=encode_fn,
             encode_shard=encode_shard)
         tp = _mark("search+fuse", tp)
+        if fused is not None:
+            outs.update(fused_ids=fused.ids, fused_scores=fused.scores,
+                        bm25_ids=fused.bm25_ids,
+                        bm25_scores=fused.bm25_scores,
+                        dense_ids=fused.dense_ids,
+                        dense_scores=fused.dense_scores)
         if rank == 0 and reranker is not None:
-            run_rerank(fused)
+            scores, top = run_rerank(fused)
+            outs.update(rerank_scores=scores, rerank_top_scores=top.values,
+                        rerank_top_idx=top.indices)
             tp = _mark("rerank", tp)
         if rank == 0 and summarizer is not None:
-            run_rag()
+            outs["rag_tokens"] = run_rag()
             tp = _mark("rag", tp)
+        return outs
 
     def sync():
         if use_gpu:
@@ -230,10 +282,11 @@ def main():
     phase_t.clear()  # drop one-time warmup costs from phase stats
     lat_ms = []
     submit_ms = []
+    last_out: dict = {}
     t0 = time.perf_counter()
     for i in range(args.steps):
         ts = time.perf_counter()
-        step(args.warmup + i)
+        last_out = step(args.warmup + i)
         submit_ms.append((time.perf_counter() - ts) * 1e3)
         if use_gpu:
             torch.cuda.synchronize()
@@ -241,6 +294,9 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     elapsed = fabric.all_reduce_max(elapsed)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out, args.seed)
 
     if rank == 0:
         total_queries = B * args.steps

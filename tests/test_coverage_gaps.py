@@ -71,9 +71,12 @@ def test_text_report_renders(tmp_path, monkeypatch):
         ctx.close()
 
 
-def test_graphed_callable_cpu_eager():
+def test_graphed_callable_cpu_eager(monkeypatch):
     import torch
     from infomesh_amd.ops.graphs import GraphedCallable
+    # the eager path is what a machine without a GPU takes; pin it so the
+    # test checks the same thing where a GPU happens to be present
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     calls = []
 
     def fn(x):

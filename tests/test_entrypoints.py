@@ -585,14 +585,20 @@ def test_bench_multi_rank_cpu_contract(tmp_path):
     import sys
     from pathlib import Path
 
+    import os
+
     root = Path(__file__).resolve().parent.parent
+    # gloo on CPU is the contract under test: hide any GPUs from the
+    # ranks, or a machine with fewer GPUs than ranks fails the launch
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1",
+               CUDA_VISIBLE_DEVICES="-1")
     proc = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29515", str(root / "bench.py"),
          "--gpus", "2", "--steps", "2", "--warmup", "1",
          "--docs-per-gpu", "5000"],
-        capture_output=True, text=True, timeout=240, cwd=root)
+        capture_output=True, text=True, timeout=240, cwd=root, env=env)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [ln for ln in proc.stdout.splitlines()
              if ln.startswith("{") and '"metric"' in ln]
@@ -601,6 +607,90 @@ def test_bench_multi_rank_cpu_contract(tmp_path):
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak"
     assert rec["config"]["parallelism"] == "shard2"
     assert rec["value"] > 0 and rec["ms_per_step"] > 0
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float32 /
+    float64 .npy files, identical from run to run for identical
+    arguments; --full is accepted and leaves the result line's contract
+    keys (and the outputs) as a plain run has them."""
+    import json as _json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    import numpy as np
+
+    root = Path(__file__).resolve().parent.parent
+    recs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        proc = subprocess.run(
+            [sys.executable, str(root / "bench.py"), "--gpus", "1",
+             "--steps", "2", "--warmup", "1", "--docs-per-gpu", "3000",
+             "--batch", "8", "--dump-outputs", str(tmp_path / name), *extra],
+            capture_output=True, text=True, timeout=240, cwd=root)
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        lines = [ln for ln in proc.stdout.splitlines()
+                 if ln.startswith("{") and '"metric"' in ln]
+        assert len(lines) == 1, proc.stdout[-2000:]
+        recs.append(_json.loads(lines[0]))
+    for rec in recs:
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype"):
+            assert key in rec
+    assert recs[0]["metric"] == recs[1]["metric"]
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["bm25_ids.npy", "bm25_scores.npy", "dense_ids.npy",
+                     "dense_scores.npy", "fused_ids.npy", "fused_scores.npy"]
+    total = 0
+    for fn in files:
+        a = np.load(tmp_path / "a" / fn)
+        b = np.load(tmp_path / "b" / fn)
+        assert a.dtype in (np.float32, np.float64)
+        assert a.shape[0] == 8 and np.isfinite(a).all()
+        assert a.shape == b.shape
+        # same inputs, same outputs, bit for bit (CPU sanity mode and
+        # the GPU kernels alike: no step sums in a racing order)
+        np.testing.assert_array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 * 1024 * 1024
+    ids = np.load(tmp_path / "a" / "fused_ids.npy")
+    assert ids.dtype == np.float64 and (ids >= 0).any()
+
+
+def test_bench_dump_outputs_budget(tmp_path):
+    """An output over its share of the 64 MB budget is cut to a fixed
+    seeded sample: same elements every time, total under the budget."""
+    import importlib.util
+    from pathlib import Path
+
+    import numpy as np
+    import torch
+
+    root = Path(__file__).resolve().parent.parent
+    spec = importlib.util.spec_from_file_location("_bench_mod",
+                                                  root / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET_BYTES == 64 * 1024 * 1024
+    bench.DUMP_BUDGET_BYTES = 1 << 20       # same rule, small arrays
+    big = torch.arange(1_000_000, dtype=torch.int64)       # 8 MB as f64
+    big2 = torch.rand(2_000_000, generator=torch.Generator().manual_seed(1))
+    small = torch.linspace(0, 1, 7)
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d),
+                           {"big": big, "big2": big2, "small": small}, seed=0)
+    bx, by = np.load(tmp_path / "x" / "big.npy"), np.load(tmp_path / "y" / "big.npy")
+    sx = np.load(tmp_path / "x" / "small.npy")
+    assert bx.dtype == np.float64 and sx.dtype == np.float32
+    np.testing.assert_array_equal(bx, by)
+    assert bx.size < big.numel() and (np.diff(bx) > 0).all()
+    np.testing.assert_array_equal(sx, small.numpy())
+    # every array over its share: the files, headers included, fit
+    bench.dump_outputs(str(tmp_path / "z"), {"a": big, "b": big2}, seed=0)
+    for d in ("x", "z"):
+        on_disk = sum(f.stat().st_size for f in (tmp_path / d).iterdir())
+        assert on_disk <= bench.DUMP_BUDGET_BYTES
 
 
 def test_session_and_analytics_thread_safety():

@@ -325,6 +325,29 @@ def test_bm25_parity():
     _assert_close(scores, ref, rtol=1e-3, atol=1e-3, what="bm25")
 
 
+def test_bm25_scores_repeat_bit_for_bit():
+    """A doc's term contributions are summed in a fixed order, so the
+    same queries give the same scores and the same hit order on every
+    run — bit for bit, also for docs matching three or more terms,
+    where a racing f32 sum would move by an ulp. Shapes: more than one
+    doc block, a doc count that is no multiple of the block, queries of
+    1, 2, 5 and 12 terms (12 > the 4 waves of a workgroup)."""
+    import numpy as np
+    from infomesh_amd.index.synth import build_synth_shard
+    shard = build_synth_shard(20_011, avg_len=60, device="cuda", seed=2,
+                              with_dense=False)
+    common = np.arange(0, 12, dtype=np.int64)      # Zipf head: dense hits
+    queries = [common, common[:5], common[3:5], common[7:8],
+               np.array([60, 3, 900, 1, 17], dtype=np.int64)]
+    first = shard.search(queries, None, k=100)
+    s0, i0 = first.bm25_scores.clone(), first.bm25_ids.clone()
+    assert (i0[0] >= 0).all() and s0[0, 0] > s0[0, -1] > 0
+    for _ in range(4):
+        h = shard.search(queries, None, k=100)
+        assert torch.equal(h.bm25_scores, s0)
+        assert torch.equal(h.bm25_ids, i0)
+
+
 def test_bm25_segmented_matches_merged():
     """Three appended segments (O(new) flush) vs one bulk build, and vs
     the post-optimize() merged segment — identical search results on the
