@@ -87,9 +87,15 @@ _SIGNATURES: dict[str, list] = {
                              c_int, c_void_p],
     "infomesh_silu_mul_fused": [c_void_p, c_void_p, c_long, c_int,
                                 c_void_p],
+    "infomesh_gemm_tile": [c_int, c_int, c_int, c_int],
 }
 
-_RESTYPES = {"infomesh_topk_workspace_u32": c_long}
+# Everything not listed here returns void. dense_scores reports
+# dispatch eligibility (0 = launched); gemm_tile the packed tile code.
+_RESTYPES = {"infomesh_topk_workspace_u32": c_long,
+             "infomesh_dense_scores": c_int,
+             "infomesh_dense_scores_fp8": c_int,
+             "infomesh_gemm_tile": c_int}
 
 
 def _try_load() -> ctypes.CDLL | None:
@@ -106,10 +112,7 @@ def _try_load() -> ctypes.CDLL | None:
     for name, argtypes in _SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        # dense_scores reports dispatch eligibility (0 = launched)
-        fn.restype = c_int if name in ("infomesh_dense_scores",
-                                       "infomesh_dense_scores_fp8") \
-            else None
+        fn.restype = _RESTYPES.get(name)
     ws = lib.infomesh_topk_workspace_u32
     ws.argtypes = [c_int]
     ws.restype = c_long

@@ -10,29 +10,10 @@
 // Replaces: the reference's torch/sentence-transformers matmuls
 // (infomesh/index/vector_store.py:120-157) and external-LLM HTTP calls
 // (infomesh/summarizer/engine.py:111-318) — see SURVEY.md §2.9.
-#include "common.h"
+#include "gemm_common.h"
 #include <cstdlib>
 
 namespace {
-
-// LDS swizzle for BK=64 tiles (involution, 16 B granules), applied to
-// the glds SOURCE address and the ds_read address (rule 21: the LDS
-// destination stays lane-linear). BK=32 rows are 64 B and keep the
-// linear image. Rows are
-// 128 B so bank_start = 32*(row&1) + 4*chunk collapses rows r and r+2
-// onto the same banks; xoring the 16 B-chunk index (bits 4-6) with
-// h(row) = (row ^ (row>>3)) & 7 (bits 7-12 of the offset) gives all 16
-// rows of a quarter-wave MFMA operand read distinct 4-bank windows.
-// Measured: the SQ_LDS_BANK_CONFLICT counter on the pipelined tile
-// (4.16e8, profiles/) is UNCHANGED by this — those conflicts come from
-// the epilogue f32 staging (4-way ds_write folding, ~192 cycles/wave-
-// tile), and wall time is glds-latency-bound either way; the swizzle is
-// kept because conflict-free operand reads cost nothing. Key uses only
-// bits >=7, which the xor never touches, so swz64(swz64(x)) == x and
-// region bases (bit 13+) pass through unchanged.
-__device__ __forceinline__ int swz64(int byte_off) {
-  return byte_off ^ ((((byte_off >> 7) ^ (byte_off >> 10)) & 7) << 4);
-}
 
 // Tile configurations (4 waves each):
 //   (128,128): 2x2 wave grid, 64x64 per wave (4x4 fragments) — default.
@@ -40,6 +21,10 @@ __device__ __forceinline__ int swz64(int byte_off) {
 //   ( 64, 64): 2x2 grid, 32x32 per wave — latency-bound small-K shapes
 //              (encoder projections) where 128^2 tiles underfill the
 //              chip and the 6-step K loop's stage latency dominates.
+//              Only K%64 != 0 lands here; K%64 == 0 takes
+//              gemm_pipe64_kernel below.
+// The BK=64 images are swizzled (swz); BK=32 rows are 64 B and keep
+// the linear image.
 template <int BM, int BN, int BK, bool OUT_F32>
 __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
@@ -72,22 +57,17 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
 
   // ---- glds staging geometry -------------------------------------------
   // One glds instruction: 64 lanes x 16 B = 1 KiB = 8 rows of BK=64 bf16
-  // (or 4 rows-pairs when BK=32: 1 KiB = 16 rows of 64 B).
+  // (or 16 rows of 64 B when BK=32).
   // A tile is BM*BK*2 bytes = BM*BK/512 KiB -> chunks of 1 KiB each.
-  constexpr int ROWS_PER_CHUNK = 1024 / (BK * 2);      // 8 (BK=64) / 16 (BK=32)
   // Chunk count follows the larger (B) tile; A stages only its first
   // BM*BK*2/1024 chunks (guarded below) when BM < BN.
   constexpr int CHUNKS = ((BM > BN ? BM : BN) * BK * 2) / 1024;
   constexpr int CHUNKS_PER_WAVE = CHUNKS / 4;
   constexpr int ACHUNKS = (BM * BK * 2) / 1024;
   constexpr int BCHUNKS2 = (BN * BK * 2) / 1024;
-  const int lanes_per_row = BK / 8;                     // 8 elements per lane
-  const int lrow = lane / lanes_per_row;
-  const int lcol = (lane % lanes_per_row) * 8;
 
   const int n_ksteps = K / BK;
 
-  constexpr int BCHUNKS = (BN * BK * 2) / 1024;      // B half count
   auto stage = [&](int buf, int kstep) {
     const long k0 = (long)kstep * BK;
 #pragma unroll
@@ -96,24 +76,18 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
       // region-relative source byte under the swizzle involution; the
       // LDS destination stays lane-linear (glds writes base + lane*16)
       const int lin = chunk * 1024 + lane * 16;
-      const int src = (BK == 64) ? swz64(lin) : lin;
+      const int src = (BK == 64) ? swz(lin) : lin;
       const int row = src / (BK * 2);
       const int colb = src % (BK * 2);
       if (chunk < BCHUNKS2) {
         int brow = n0 + row; brow = brow < N ? brow : N - 1;
-        const bf16* gb = Bg + (long)brow * K + k0 + colb / 2;
-        auto* lb = (__attribute__((address_space(3))) unsigned int*)
-            &smem[buf][BM * BK + chunk * 512];
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) unsigned int*)gb, lb, 16, 0, 0);
+        glds16<0>(Bg + (long)brow * K + k0 + colb / 2,
+                  &smem[buf][BM * BK + chunk * 512]);
       }
       if (chunk < ACHUNKS) {
         int arow = m0 + row; arow = arow < M ? arow : M - 1;
-        const bf16* ga = Ag + (long)arow * K + k0 + colb / 2;
-        auto* la = (__attribute__((address_space(3))) unsigned int*)
-            &smem[buf][chunk * 512];
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) unsigned int*)ga, la, 16, 0, 0);
+        glds16<0>(Ag + (long)arow * K + k0 + colb / 2,
+                  &smem[buf][chunk * 512]);
       }
     }
   };
@@ -142,7 +116,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
         const int off = (row * BK + ks * 32 + fk) * 2;
         a[i] = *reinterpret_cast<const bf16x8*>(
             (const char*)&smem[cur][0]
-            + ((BK == 64) ? swz64(off) : off));
+            + ((BK == 64) ? swz(off) : off));
       }
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
         const int off = (row * BK + ks * 32 + fk) * 2;
         b[j] = *reinterpret_cast<const bf16x8*>(
             (const char*)&smem[cur][BM * BK]
-            + ((BK == 64) ? swz64(off) : off));
+            + ((BK == 64) ? swz(off) : off));
       }
 #pragma unroll
       for (int i = 0; i < FM; ++i)
@@ -164,73 +138,23 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
   }
 
   // ---- epilogue ---------------------------------------------------------
-  // Huge-N f32 output (the dense scoring plane): stage the wave's
-  // 64-col row segments through LDS and emit 16-B dwordx4 stores,
-  // NONTEMPORAL — C is written once and next read by the streaming
-  // top-k, so allocating it in L2 only evicts the B rows being
-  // streamed. Smaller/bf16 outputs keep the direct scalar path.
-  const int crow_base = (lane >> 4) * 4;
-  const int ccol = lane & 15;
-  if (OUT_F32 && (BN == 128 || BN == 64) && n0 + BN <= N
-      && m0 + BM <= M) {
+  // Full f32 tiles (the dense scoring plane is huge-N f32) go out
+  // through the LDS-staged nontemporal path; partial tiles and bf16
+  // outputs keep the direct scalar path.
+  const int m_base = m0 + wm * (BM / WM), n_base = n0 + wn * (BN / WN);
+  if (OUT_F32 && n0 + BN <= N && m0 + BM <= M) {
     // reuse the (drained) double buffer as an f32 staging tile:
     // per wave a [BM/WM][BN/WN] block = 64x64 (or 64x32/32x32) f32
     float* stage_f32 = reinterpret_cast<float*>(&smem[0][0])
         + wid * (BM / WM) * (BN / WN);
     __syncthreads();   // all MFMA reads of smem are done
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int lm = i * 16 + crow_base + r;      // wave-local row
-          const int ln = j * 16 + ccol;               // wave-local col
-          const int n = n0 + wn * (BN / WN) + ln;
-          const float bv = bias ? bias[n] : 0.0f;
-          stage_f32[lm * (BN / WN) + ln] =
-              apply_act(alpha * acc[i][j][r] + bv, act);
-        }
-    __builtin_amdgcn_s_waitcnt(0);  // lgkmcnt: LDS writes visible
-    __builtin_amdgcn_wave_barrier();
-    // each lane streams 16 B of a row segment: WAVEN cols * 4 B / 16
-    constexpr int SEGN = BN / WN;                  // cols per wave block
-    constexpr int LPR = SEGN * 4 / 16;             // lanes per row
-    constexpr int ROWS_PER_IT = 64 / LPR;
-    const int srow = lane / LPR, scol4 = (lane % LPR) * 4;
-#pragma unroll
-    for (int base = 0; base < BM / WM; base += ROWS_PER_IT) {
-      const int lm = base + srow;
-      const int m = m0 + wm * (BM / WM) + lm;
-      const int n = n0 + wn * SEGN + scol4;
-      f32x4 v = *reinterpret_cast<const f32x4*>(
-          &stage_f32[lm * SEGN + scol4]);
-      __builtin_nontemporal_store(
-          v, reinterpret_cast<f32x4*>(
-              reinterpret_cast<float*>(C)
-              + (long)g * strideC + (long)m * N + n));
-    }
+    store_frags_staged_f32(acc, stage_f32, reinterpret_cast<float*>(C),
+                           (long)g * strideC, bias, m_base, n_base, N,
+                           act, alpha, lane);
     return;
   }
-#pragma unroll
-  for (int i = 0; i < FM; ++i) {
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int n = n0 + wn * (BN / WN) + j * 16 + ccol;
-      if (n >= N) continue;
-      const float bv = bias ? bias[n] : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * (BM / WM) + i * 16 + crow_base + r;
-        if (m >= M) continue;
-        float v = apply_act(alpha * acc[i][j][r] + bv, act);
-        if (OUT_F32)
-          reinterpret_cast<float*>(C)[(long)g * strideC + (long)m * N + n] = v;
-        else
-          reinterpret_cast<bf16*>(C)[(long)g * strideC + (long)m * N + n] = f2bf(v);
-      }
-    }
-  }
+  store_frags_guarded<OUT_F32>(acc, C, (long)g * strideC, bias,
+                               m_base, n_base, M, N, N, act, alpha, lane);
 }
 
 // ---- 3-buffer glds-span pipelined 64x64 tile ---------------------------
@@ -242,14 +166,16 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
 // serial at 1-block/CU), and 16 KiB/buffer keeps 3 workgroups resident
 // per CU on top. Round-1 BACKLOG item "counted-vmcnt small-tile
 // pipeline (gemm8-style scheduling at 64^2)".
-template <int BNT, bool OUT_F32>
+// (A 64x128 variant ran the full encoder in 1278 vs 990 us: 2 WGs/CU
+// lose more than the wider MFMA blocks gain — see BACKLOG.)
+template <bool OUT_F32>
 __global__ __launch_bounds__(256) void gemm_pipe64_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     void* __restrict__ C, const float* __restrict__ bias,
     int M, int N, int K,
     long strideA, long strideB, long strideC,
     int act, float alpha) {
-  constexpr int BM = 64, BN = BNT, BK = 64;
+  constexpr int BM = 64, BN = 64, BK = 64;
   __shared__ bf16 smem[3][(BM + BN) * BK];   // 3 x 16 KiB
 
   const int tiles_n = (N + BN - 1) / BN;
@@ -276,7 +202,7 @@ __global__ __launch_bounds__(256) void gemm_pipe64_kernel(
     for (int c = 0; c < CPW; ++c) {
       const int chunk = wid * CPW + c;
       const int lin = chunk * 1024 + lane * 16;
-      const int src = swz64(lin);
+      const int src = swz(lin);
       const int row = src / (BK * 2);
       const int colb = src % (BK * 2);
       const bool is_b = chunk >= (BM * BK * 2 / 1024);
@@ -284,15 +210,11 @@ __global__ __launch_bounds__(256) void gemm_pipe64_kernel(
       const int lim = is_b ? N : M;
       grow = grow < lim ? grow : lim - 1;
       const bf16* gsrc = (is_b ? Bg : Ag) + (long)grow * K + k0 + colb / 2;
-      auto* dst = (__attribute__((address_space(3))) unsigned int*)
-          ((char*)&smem[buf][0] + (long)chunk * 1024);
       // NT on the A loads was tried here (gemm8-style): encoder
       // 993 -> 1135 us. At these shapes BOTH operands fit the XCD L2
       // together (A 3.1 MB x 18-way n-reuse + B 0.9 MB), so the NT
       // hint only destroyed A's own reuse. Keep default caching.
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)gsrc,
-          dst, 16, 0, 0);
+      glds16<0>(gsrc, (char*)&smem[buf][0] + (long)chunk * 1024);
     }
   };
 
@@ -319,7 +241,7 @@ __global__ __launch_bounds__(256) void gemm_pipe64_kernel(
       for (int ks = 0; ks < 2; ++ks) {
         const int row = wm * 32 + i * 16 + fr;
         a[i][ks] = *reinterpret_cast<const bf16x8*>(
-            abase + swz64((row * BK + ks * 32 + fk) * 2));
+            abase + swz((row * BK + ks * 32 + fk) * 2));
       }
 #pragma unroll
     for (int j = 0; j < FN; ++j)
@@ -327,7 +249,7 @@ __global__ __launch_bounds__(256) void gemm_pipe64_kernel(
       for (int ks = 0; ks < 2; ++ks) {
         const int brow = wn * (BN / 2) + j * 16 + fr;
         b[j][ks] = *reinterpret_cast<const bf16x8*>(
-            bbase + swz64((brow * BK + ks * 32 + fk) * 2));
+            bbase + swz((brow * BK + ks * 32 + fk) * 2));
       }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -349,145 +271,96 @@ __global__ __launch_bounds__(256) void gemm_pipe64_kernel(
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  const int crow_base = (lane >> 4) * 4;
-  const int ccol = lane & 15;
   constexpr int SEGN = BN / 2;
+  const int m_base = m0 + wm * 32, n_base = n0 + wn * SEGN;
   if (OUT_F32 && n0 + BN <= N && m0 + BM <= M) {
-    // staged dwordx4 nontemporal epilogue (see the generic tile)
     float* stage_f32 = reinterpret_cast<float*>(&smem[0][0])
         + wid * 32 * SEGN;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int lm = i * 16 + crow_base + r;
-          const int ln = j * 16 + ccol;
-          const float bv = bias ? bias[n0 + wn * SEGN + ln] : 0.0f;
-          stage_f32[lm * SEGN + ln] =
-              apply_act(alpha * acc[i][j][r] + bv, act);
-        }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    constexpr int LPR = SEGN / 4;
-    constexpr int RPI = 64 / LPR;
-    const int srow = lane / LPR, scol4 = (lane % LPR) * 4;
-#pragma unroll
-    for (int base = 0; base < 32; base += RPI) {
-      const int lm = base + srow;
-      const int m = m0 + wm * 32 + lm;
-      const int n = n0 + wn * SEGN + scol4;
-      f32x4 v = *reinterpret_cast<const f32x4*>(
-          &stage_f32[lm * SEGN + scol4]);
-      __builtin_nontemporal_store(
-          v, reinterpret_cast<f32x4*>(
-              reinterpret_cast<float*>(C)
-              + (long)g * strideC + (long)m * N + n));
-    }
+    store_frags_staged_f32(acc, stage_f32, reinterpret_cast<float*>(C),
+                           (long)g * strideC, bias, m_base, n_base, N,
+                           act, alpha, lane);
     return;
   }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int n = n0 + wn * SEGN + j * 16 + ccol;
-      if (n >= N) continue;
-      const float bv = bias ? bias[n] : 0.0f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm * 32 + i * 16 + crow_base + r;
-        if (m >= M) continue;
-        float v = apply_act(alpha * acc[i][j][r] + bv, act);
-        if (OUT_F32)
-          reinterpret_cast<float*>(C)[(long)g * strideC + (long)m * N + n] = v;
-        else
-          reinterpret_cast<bf16*>(C)[(long)g * strideC + (long)m * N + n] =
-              f2bf(v);
-      }
-    }
-  }
+  store_frags_guarded<OUT_F32>(acc, C, (long)g * strideC, bias,
+                               m_base, n_base, M, N, N, act, alpha, lane);
 }
 
-}  // namespace
+// ---- host side ---------------------------------------------------------
+using GemmKernel = void (*)(const bf16*, const bf16*, void*, const float*,
+                            int, int, int, long, long, long, int, float);
 
-extern "C" void infomesh_gemm_bf16_nt(
-    const void* A, const void* B, void* C, const void* bias,
-    int M, int N, int K, int batch,
-    long strideA, long strideB, long strideC,
-    int act, float alpha, int out_f32, void* stream) {
-  auto s = reinterpret_cast<hipStream_t>(stream);
-  const bool bk64 = (K % 64 == 0);
+template <int BM, int BN, int BK>
+GemmKernel generic_kernel(bool out_f32) {
+  return out_f32 ? gemm_bf16_nt_kernel<BM, BN, BK, true>
+                 : gemm_bf16_nt_kernel<BM, BN, BK, false>;
+}
+
+struct GemmTile {
+  int bm, bn, bk;
+  bool pipe;   // gemm_pipe64_kernel instead of the generic tile
+};
+
+// Tile heuristic. force is the INFOMESH_GEMM_TILE value (64 or 128
+// forces that tile, anything else leaves the choice alone).
+GemmTile pick_tile(int M, int N, int K, int batch, int force) {
   int bm = (M <= 64) ? 64 : 128, bn = 128;
   // Latency-bound regime: few K-steps and not enough 128^2 tiles to
   // fill the chip -> quarter tiles for 4x the block-level overlap.
   const long blocks128 =
       (long)((M + 127) / 128) * ((N + 127) / 128) * batch;
   if (bm == 128 && blocks128 < 512 && K <= 2048) bm = bn = 64;
-  // Tuning override (read once): INFOMESH_GEMM_TILE=64|128 forces the
-  // tile; scripts/gemm_tile_probe.py uses it to validate the heuristic.
+  if (force == 64 && M > 64) bm = bn = 64;
+  else if (force == 128) bm = bn = 128;
+  // (BK=128 for the 64^2 tile was probe-tested and is ~60% SLOWER:
+  // doubling LDS to 64 KB halves resident blocks per CU, which costs
+  // more latency hiding than the halved K-step drains save.)
+  const int bk = (K % 64 == 0) ? 64 : 32;
+  // 64^2 with whole 64-deep K-steps: the 3-buffer glds-span pipeline
+  return {bm, bn, bk, bm == 64 && bn == 64 && bk == 64};
+}
+
+GemmKernel tile_kernel(GemmTile t, bool out_f32) {
+  if (t.pipe)
+    return out_f32 ? gemm_pipe64_kernel<true> : gemm_pipe64_kernel<false>;
+  if (t.bn == 64) return generic_kernel<64, 64, 32>(out_f32);
+  if (t.bm == 64)
+    return t.bk == 64 ? generic_kernel<64, 128, 64>(out_f32)
+                      : generic_kernel<64, 128, 32>(out_f32);
+  return t.bk == 64 ? generic_kernel<128, 128, 64>(out_f32)
+                    : generic_kernel<128, 128, 32>(out_f32);
+}
+
+// Tuning override (read once): INFOMESH_GEMM_TILE=64|128 forces the
+// tile; scripts/gemm_tile_probe.py uses it to validate the heuristic.
+int tile_override() {
   static const int ov = [] {
     const char* e = getenv("INFOMESH_GEMM_TILE");
     return e ? atoi(e) : -1;
   }();
-  if (ov == 64 && M > 64) bm = bn = 64;
-  else if (ov == 128) { bm = 128; bn = 128; }
-  const int tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-  dim3 grid(tiles, batch);
-  dim3 block(256);
-#define LAUNCH(BMV, BNV, BKV, OF)                                            \
-  hipLaunchKernelGGL((gemm_bf16_nt_kernel<BMV, BNV, BKV, OF>), grid, block,  \
-                     0, s, (const bf16*)A, (const bf16*)B, C,                \
-                     (const float*)bias, M, N, K, strideA, strideB,          \
-                     strideC, act, alpha)
-#define PICK(BMV, BNV)                                                       \
-  do {                                                                       \
-    if (bk64) { if (out_f32) LAUNCH(BMV, BNV, 64, true);                     \
-                else LAUNCH(BMV, BNV, 64, false); }                          \
-    else      { if (out_f32) LAUNCH(BMV, BNV, 32, true);                     \
-                else LAUNCH(BMV, BNV, 32, false); }                          \
-  } while (0)
-  // (BK=128 for the 64^2 tile was probe-tested and is ~60% SLOWER:
-  // doubling LDS to 64 KB halves resident blocks per CU, which costs
-  // more latency hiding than the halved K-step drains save.)
-  static const int pipe_ov = [] {
-    const char* e = getenv("INFOMESH_GEMM_PIPE");
-    return e ? atoi(e) : 1;
-  }();
-  if (bm == 64 && bn == 64 && bk64 && pipe_ov) {
-    // latency-bound regime: 3-buffer glds-span pipeline; BN=128 when N
-    // has whole 128-tiles (pipe_ov=2 forces BN=64, =3 forces BN=128)
-    // BN=128 measured SLOWER on the encoder shapes (1278 vs 990 us
-    // full-encoder: 2 WGs/CU vs 3 loses more than wider MFMA gains);
-    // kept behind =3 for future shapes
-    const bool wide = (pipe_ov == 3);
-    if (wide) {
-      const int tiles_w = ((M + 63) / 64) * ((N + 127) / 128);
-      dim3 gw(tiles_w, batch);
-      if (out_f32)
-        hipLaunchKernelGGL((gemm_pipe64_kernel<128, true>), gw, block,
-                           0, s, (const bf16*)A, (const bf16*)B, C,
-                           (const float*)bias, M, N, K, strideA,
-                           strideB, strideC, act, alpha);
-      else
-        hipLaunchKernelGGL((gemm_pipe64_kernel<128, false>), gw, block,
-                           0, s, (const bf16*)A, (const bf16*)B, C,
-                           (const float*)bias, M, N, K, strideA,
-                           strideB, strideC, act, alpha);
-    } else if (out_f32)
-      hipLaunchKernelGGL((gemm_pipe64_kernel<64, true>), grid, block, 0, s,
-                         (const bf16*)A, (const bf16*)B, C,
-                         (const float*)bias, M, N, K, strideA, strideB,
-                         strideC, act, alpha);
-    else
-      hipLaunchKernelGGL((gemm_pipe64_kernel<64, false>), grid, block, 0, s,
-                         (const bf16*)A, (const bf16*)B, C,
-                         (const float*)bias, M, N, K, strideA, strideB,
-                         strideC, act, alpha);
-  }
-  else if (bm == 64 && bn == 64) PICK(64, 64);
-  else if (bm == 64) PICK(64, 128);
-  else PICK(128, 128);
-#undef PICK
-#undef LAUNCH
+  return ov;
 }
+
+}  // namespace
+
+// The tile infomesh_gemm_bf16_nt runs this shape on, packed as
+// bm | bn << 8 | bk << 16 | pipe << 24 (tests pin their shapes to a
+// kernel with it).
+extern "C" int infomesh_gemm_tile(int M, int N, int K, int batch) {
+  const GemmTile t = pick_tile(M, N, K, batch, tile_override());
+  return t.bm | t.bn << 8 | t.bk << 16 | (int)t.pipe << 24;
+}
+
+extern "C" void infomesh_gemm_bf16_nt(
+    const void* A, const void* B, void* C, const void* bias,
+    int M, int N, int K, int batch,
+    long strideA, long strideB, long strideC,
+    int act, float alpha, int out_f32, void* stream) {
+  const GemmTile t = pick_tile(M, N, K, batch, tile_override());
+  const int tiles = ((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn);
+  hipLaunchKernelGGL(tile_kernel(t, out_f32), dim3(tiles, batch), dim3(256),
+                     0, reinterpret_cast<hipStream_t>(stream),
+                     (const bf16*)A, (const bf16*)B, C, (const float*)bias,
+                     M, N, K, strideA, strideB, strideC, act, alpha);
+}
+
+

@@ -9,6 +9,7 @@ because they launch on torch's current (capture) stream.
 """
 from __future__ import annotations
 
+import gc
 import logging
 from typing import Callable
 
@@ -58,7 +59,16 @@ class GraphedCallable:
                 out = self.fn(*static_in)
         torch.cuda.current_stream().wait_stream(stream)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            static_out = self.fn(*static_in)
+        # No cyclic GC while the stream captures: a collection that
+        # finalizes some earlier graph, stream or event calls into HIP
+        # mid-capture, which aborts the process.
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph):
+                static_out = self.fn(*static_in)
+        finally:
+            if gc_was_enabled:
+                gc.enable()
         del out
         return graph, static_in, static_out

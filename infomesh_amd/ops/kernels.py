@@ -23,6 +23,31 @@ def _check(t: torch.Tensor, dtype: torch.dtype, name: str) -> None:
     assert t.is_contiguous(), f"{name} must be contiguous"
 
 
+def gemm_route(M: int, N: int, K: int, G: int) -> str:
+    """Which kernel family gemm_nt runs a [G,M,K] x [N,K] product on."""
+    if M <= 16:
+        # skinny-M decode path: wave-per-column GEMV (csrc/gemv.hip)
+        return "gemv"
+    if (M >= 4096 and N >= 512 and K % 64 == 0
+            and ((M + 255) // 256) * ((N + 255) // 256) * max(G, 1) >= 224):
+        # big projection shapes: deep-pipelined 256x256 tile (gemm8.hip)
+        # (tile count must fill the chip at 1 block/CU)
+        return "gemm8"
+    return "gemm"
+
+
+# route -> C entry point; the three share one signature
+_GEMM_ENTRY = {"gemv": "infomesh_gemv_bf16_nt",
+               "gemm8": "infomesh_gemm8_bf16_nt",
+               "gemm": "infomesh_gemm_bf16_nt"}
+
+
+def gemm_tile(M: int, N: int, K: int, G: int) -> tuple[int, int, int, bool]:
+    """(bm, bn, bk, pipelined) of the gemm.hip tile for this shape."""
+    code = _ext.lib().infomesh_gemm_tile(M, N, K, G)
+    return code & 0xff, code >> 8 & 0xff, code >> 16 & 0xff, bool(code >> 24)
+
+
 def gemm_nt(a: torch.Tensor, b: torch.Tensor,
             bias: torch.Tensor | None = None,
             act: str = "none", alpha: float = 1.0,
@@ -56,25 +81,10 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor,
         out = torch.empty((G, M, N), device=a.device, dtype=dtype)
     else:
         assert out.shape == (G, M, N) and out.dtype == dtype and out.is_contiguous()
-    if M <= 16:
-        # skinny-M decode path: wave-per-column GEMV (csrc/gemv.hip)
-        _ext.lib().infomesh_gemv_bf16_nt(
-            a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(bias),
-            M, N, K, G, M * K, strideB, M * N,
-            ACT[act], alpha, int(out_f32), _ext.stream_ptr())
-    elif (M >= 4096 and N >= 512 and K % 64 == 0
-          and ((M + 255) // 256) * ((N + 255) // 256) * max(G, 1) >= 224):
-        # big projection shapes: deep-pipelined 256x256 tile (gemm8.hip)
-        # (tile count must fill the chip at 1 block/CU)
-        _ext.lib().infomesh_gemm8_bf16_nt(
-            a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(bias),
-            M, N, K, G, M * K, strideB, M * N,
-            ACT[act], alpha, int(out_f32), _ext.stream_ptr())
-    else:
-        _ext.lib().infomesh_gemm_bf16_nt(
-            a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(bias),
-            M, N, K, G, M * K, strideB, M * N,
-            ACT[act], alpha, int(out_f32), _ext.stream_ptr())
+    fn = getattr(_ext.lib(), _GEMM_ENTRY[gemm_route(M, N, K, G)])
+    fn(a.data_ptr(), b.data_ptr(), out.data_ptr(), _ptr(bias),
+       M, N, K, G, M * K, strideB, M * N,
+       ACT[act], alpha, int(out_f32), _ext.stream_ptr())
     return out.squeeze(0) if sq_a else out
 
 

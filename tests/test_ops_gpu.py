@@ -53,6 +53,38 @@ def test_gemm_nt_shapes(M, N, Kd):
                   what=f"gemm {M}x{N}x{Kd}")
 
 
+@pytest.mark.parametrize("M,N,Kd,bias_silu,out_f32,tile", [
+    # 128^2, BK=64, full tiles: the LDS-staged f32 epilogue
+    (128, 256, 2112, False, True, (128, 128, 64, False)),
+    # 128^2, BK=64, partial tiles
+    (130, 200, 2112, True, False, (128, 128, 64, False)),
+    # 128^2, BK=32
+    (130, 200, 2080, False, False, (128, 128, 32, False)),
+    # 64x128, BK=64, staged f32
+    (64, 256, 128, False, True, (64, 128, 64, False)),
+    # pipelined 64^2, three K-steps: all three buffers rotate
+    (192, 192, 192, False, False, (64, 64, 64, True)),
+    # M <= 64 takes the 64x128 tile, never the pipelined one
+    (64, 64, 64, False, False, (64, 128, 64, False)),
+])
+def test_gemm_tile_variants(M, N, Kd, bias_silu, out_f32, tile):
+    """One case per gemm.hip kernel variant the other tests do not pin;
+    the tile assertion keeps a heuristics change from moving a case to
+    another kernel unnoticed."""
+    assert K.gemm_route(M, N, Kd, 1) == "gemm"
+    assert K.gemm_tile(M, N, Kd, 1) == tile
+    a = torch.randn(M, Kd, device="cuda").bfloat16()
+    b = torch.randn(N, Kd, device="cuda").bfloat16()
+    bias = torch.randn(N, device="cuda") if bias_silu else None
+    act = "silu" if bias_silu else "none"
+    out = K.gemm_nt(a, b, bias=bias, act=act, out_f32=out_f32)
+    assert out.dtype == (torch.float32 if out_f32 else torch.bfloat16)
+    ref = R.gemm_nt(a.cpu(), b.cpu(),
+                    bias.cpu() if bias_silu else None, act=act)
+    _assert_close(out, ref, rtol=3e-2, atol=Kd ** 0.5 * 2e-2,
+                  what=f"gemm {M}x{N}x{Kd} tile {tile}")
+
+
 @pytest.mark.parametrize("M,N,Kd", [(1, 9216, 3072), (4, 100, 64),
                                     (16, 32064, 3072), (8, 3072, 8192)])
 def test_gemv_skinny_m(M, N, Kd):
@@ -575,27 +607,63 @@ def test_kv_append():
     assert kc[0, :, 4].abs().sum() == 0
 
 
-@pytest.mark.parametrize("M,N,Kd", [(4096, 512, 384), (4500, 2304, 768),
-                                    (4096, 513, 128)])
-def test_gemm8_large_shapes(M, N, Kd):
-    """M>=4096 dispatches to the deep-pipelined 256x256 kernel."""
-    a = torch.randn(M, Kd, device="cuda").bfloat16()
+@pytest.mark.parametrize("G,M,N,Kd,bias_gelu,out_f32", [
+    # full tiles only (16x14 = 224): bf16 staged epilogue, two K-steps
+    (1, 4096, 3584, 128, True, False),
+    # one K-step: every prefetch past it is clamped
+    (1, 4096, 3584, 64, False, False),
+    # 17x14 tiles with partial last row/column tiles: guarded scalar
+    # epilogue, odd K-step count; bf16 then f32 output
+    (1, 4097, 3330, 192, True, False),
+    (1, 4097, 3330, 192, True, True),
+    # batched over a shared 2-D B (strideB == 0): 16x2x7 = 224 tiles
+    (7, 4096, 512, 128, False, False),
+])
+def test_gemm8_large_shapes(G, M, N, Kd, bias_gelu, out_f32):
+    """Shapes with >= 224 tiles of 256x256 run the deep-pipelined kernel."""
+    assert K.gemm_route(M, N, Kd, G) == "gemm8"
+    a = torch.randn(*((G,) if G > 1 else ()), M, Kd, device="cuda").bfloat16()
     b = torch.randn(N, Kd, device="cuda").bfloat16()
-    bias = torch.randn(N, device="cuda")
-    out = K.gemm_nt(a, b, bias=bias, act="gelu")
-    ref = R.gemm_nt(a.cpu(), b.cpu(), bias.cpu(), act="gelu")
+    bias = torch.randn(N, device="cuda") if bias_gelu else None
+    act = "gelu" if bias_gelu else "none"
+    out = K.gemm_nt(a, b, bias=bias, act=act, out_f32=out_f32)
+    assert out.dtype == (torch.float32 if out_f32 else torch.bfloat16)
+    ref = R.gemm_nt(a.cpu(), b.cpu(),
+                    bias.cpu() if bias_gelu else None, act=act)
     _assert_close(out, ref, rtol=3e-2, atol=Kd ** 0.5 * 2e-2,
-                  what=f"gemm8 {M}x{N}x{Kd}")
+                  what=f"gemm8 {G}x{M}x{N}x{Kd}")
 
 
 def test_gemm8_transpose_check():
-    M, N, Kd = 4096, 512, 64
+    M, N, Kd = 4096, 3584, 64
+    assert K.gemm_route(M, N, Kd, 1) == "gemm8"
     a = torch.eye(M, Kd, device="cuda").bfloat16()
     b = (torch.arange(N * Kd, device="cuda").reshape(N, Kd).bfloat16()
          / (N * Kd))
     out = K.gemm_nt(a, b)
     ref = R.gemm_nt(a.cpu(), b.cpu())
     _assert_close(out, ref, what="gemm8 transpose check")
+
+
+def test_gemm8_n_chunked(monkeypatch):
+    """INFOMESH_GEMM8_CHUNK=1 splits a B panel above 3 MB into column
+    chunks (here 1536 + 1536 + 512 of N=3584), each launched with its
+    own B, bias and C offset and the full row stride. Every element sees
+    the same K order as in the single launch, so the two are bit-equal."""
+    M, N, Kd = 4096, 3584, 768
+    assert K.gemm_route(M, N, Kd, 1) == "gemm8"
+    a = torch.randn(M, Kd, device="cuda").bfloat16()
+    b = torch.randn(N, Kd, device="cuda").bfloat16()
+    bias = torch.randn(N, device="cuda")
+    monkeypatch.delenv("INFOMESH_GEMM8_CHUNK", raising=False)
+    whole = K.gemm_nt(a, b, bias=bias)
+    monkeypatch.setenv("INFOMESH_GEMM8_CHUNK", "1")
+    chunked = K.gemm_nt(a, b, bias=bias)
+    torch.cuda.synchronize()
+    ref = R.gemm_nt(a.cpu(), b.cpu(), bias.cpu())
+    _assert_close(chunked, ref, rtol=3e-2, atol=Kd ** 0.5 * 2e-2,
+                  what="gemm8 chunked")
+    assert torch.equal(chunked, whole)
 
 
 def test_topk_sampled_vs_exact():

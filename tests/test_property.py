@@ -681,7 +681,11 @@ def test_rag_chunking_covers_and_bounds(passages, max_chunks):
                             chunk_size=64 * max_chunks)
     assert out.chunks is not None
     def norm(x):
-        return "".join(c for c in x if c.isprintable()).strip()
+        # the chunker splits on whitespace and rejoins with one space,
+        # so any whitespace run ('\r' included) equals a single space
+        words = ("".join(c for c in w if c.isprintable())
+                 for w in x.split())
+        return " ".join(w for w in words if w)
     for ch in out.chunks:
         # chunk text derives from the snippets (chunker may normalize
         # whitespace/control chars and truncate)
