@@ -127,6 +127,11 @@ class GpuShard:
         self._emb_buf: torch.Tensor | None = None   # [cap, D] bf16 (unit)
         self._gid_buf: torch.Tensor | None = None   # [cap] i64
         self._topk = None
+        self._topk_dense = None
+        self._dense_graphs: dict = {}
+        # hipGraph-capture the dense plane; set by the overlapped query
+        # plane, off for direct search() callers
+        self.graph_dense = False
         self._h_idf: np.ndarray | None = None
         # pending (un-built) batch buffers — the ingest side-buffer;
         # GPU visibility flips at build() (epoch-style).
@@ -441,7 +446,7 @@ class GpuShard:
         """Separate selector (own workspace) so the dense plane can run
         on a different stream than the BM25 plane without racing."""
         from ..ops.kernels import TopK
-        if getattr(self, "_topk_dense", None) is None:
+        if self._topk_dense is None:
             self._topk_dense = TopK(self.device)
         return self._topk_dense
 
@@ -648,40 +653,23 @@ class GpuShard:
         N = self.n_docs
         k = min(k, N)
         tp = _time.perf_counter()
-        tk = self._get_topk_dense()
         emb = self.embeddings
         # hipGraph capture of the whole plane (GEMM + top-k passes, all
-        # fixed shapes) removes ~10 launch gaps per batch. Only when the
-        # caller runs deferred top-k verification (the query plane does):
-        # the eager path reads the overflow flag (D2H), which is illegal
-        # inside a capture. Graphs are invalidated on every append
+        # fixed shapes) removes ~10 launch gaps per batch. Opt-in per
+        # shard (graph_dense). Graphs are invalidated on every append
         # (the captured embeddings view goes stale).
-        if self.device.type == "cuda" and tk.defer_check:
-            key = (B, k)
-            graphs = getattr(self, "_dense_graphs", None)
-            if graphs is None:
-                graphs = self._dense_graphs = {}
-            entry = graphs.get(key)
-            if entry is None:
+        if self.device.type == "cuda" and self.graph_dense:
+            g = self._dense_graphs.get((B, k))
+            if g is None:
                 from ..ops.graphs import GraphedCallable
 
-                def _plane(e, _B=B, _k=k, _emb=emb):
-                    d = self._dense_gemm(e, _emb, _B, self.n_docs)
-                    return tk(d, _k)
-                g = GraphedCallable(_plane)
-                vals, idx = g(query_emb.bfloat16())  # captures
-                # pin the capture-time workspace: replays write THIS
-                # tensor even if tk._ws is later reallocated
-                entry = (g, tk._ws)
-                graphs[key] = entry
-            else:
-                g, ws = entry
-                vals, idx = g(query_emb.bfloat16())
-                # Graph replay skips the wrapper's python, so re-arm
-                # the deferred overflow check by hand (same static
-                # workspace/layout as at capture; need=0 -> exact).
-                tk._pending.append((ws, K.topk_cnt_off(B),
-                                    K.topk_flag_off(B), B, 0))
+                # A selector of its own per graph: replays keep writing
+                # the workspace recorded at capture, which a selector
+                # shared across batch sizes would free when it regrows.
+                def _plane(e, _B=B, _k=k, _emb=emb, _tk=K.TopK(self.device)):
+                    return _tk(self._dense_gemm(e, _emb, _B, self.n_docs), _k)
+                g = self._dense_graphs[(B, k)] = GraphedCallable(_plane)
+            vals, idx = g(query_emb.bfloat16())
             # detach from the graph's static outputs (next replay
             # overwrites them)
             out = (vals.clone(), idx.clone())
@@ -689,12 +677,7 @@ class GpuShard:
             return out
         d_scores = self._dense_gemm(query_emb, emb, B, N)
         tp = mark("shard.dense", tp)
-        # Always exact select. The sampled-threshold variant was measured
-        # a net loss at every shard size: the candidate slack (~Kp*stride)
-        # inflates the final bitonic sort by more than the 2 saved passes
-        # (~80us/pass at 1.25M docs), and with an 8192-sample + 8192-cap
-        # it is only statistically sound for N <~ 2.7M anyway.
-        out = tk(d_scores, k)
+        out = self._get_topk_dense()(d_scores, k)
         mark("shard.densetopk", tp)
         return out
 

@@ -40,7 +40,9 @@ _SIGNATURES: dict[str, list] = {
                       c_int, c_int, c_void_p],
     "infomesh_argmax": [c_void_p, c_void_p, c_long, c_int, c_void_p],
     "infomesh_topk": [c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                      c_long, c_int, c_int, c_void_p, c_void_p],
+                      c_long, c_int, c_void_p, c_void_p],
+    "infomesh_topk_workspace_u32": [c_int],
+    "infomesh_topk_zero_u32": [c_int],
     "infomesh_bm25_block": [c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_int, c_int, c_long,
@@ -90,9 +92,10 @@ _SIGNATURES: dict[str, list] = {
     "infomesh_gemm_tile": [c_int, c_int, c_int, c_int],
 }
 
-# Everything not listed here returns void. dense_scores reports
-# dispatch eligibility (0 = launched); gemm_tile the packed tile code.
+# Everything not listed here returns void. topk_*_u32: lengths;
+# dense_scores: dispatch eligibility (0 = launched); gemm_tile: tile code.
 _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
+             "infomesh_topk_zero_u32": c_long,
              "infomesh_dense_scores": c_int,
              "infomesh_dense_scores_fp8": c_int,
              "infomesh_gemm_tile": c_int}
@@ -113,9 +116,6 @@ def _try_load() -> ctypes.CDLL | None:
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = _RESTYPES.get(name)
-    ws = lib.infomesh_topk_workspace_u32
-    ws.argtypes = [c_int]
-    ws.restype = c_long
     import os
     if os.environ.get("INFOMESH_SYNC_DEBUG"):
         return _SyncDebugLib(lib)

@@ -90,12 +90,10 @@ __global__ __launch_bounds__(256) void bm25_block_kernel(
   const int blk = blockIdx.y;
   const long d0 = (long)blk * BD;
   const int nd = (int)min((long)BD, nseg - d0);
-  // 8 padded histogram copies after the score tile (same bank spread
-  // as topk.hip hist1_kernel: 264-int stride)
+  // padded histogram copies (common.h hist8_*) after the score tile
   unsigned* lh = reinterpret_cast<unsigned*>(lds_scores + BD);
   for (int i = threadIdx.x; i < nd; i += blockDim.x) lds_scores[i] = 0.0f;
-  if (HIST)
-    for (int i = threadIdx.x; i < 8 * 264; i += blockDim.x) lh[i] = 0;
+  if (HIST) hist8_zero(lh);
   __syncthreads();
   const int t0 = qt_off[q], t1 = qt_off[q + 1];
   // query-term tuples one after another, the whole workgroup striding
@@ -135,7 +133,7 @@ __global__ __launch_bounds__(256) void bm25_block_kernel(
       __builtin_nontemporal_store(lds_scores[i], srow + i);
     return;
   }
-  unsigned* my = lh + (threadIdx.x & 7) * 264;
+  unsigned* my = hist8_mine(lh);
   unsigned zc = 0;  // zero scores dominate: aggregate in a register
   for (int i = threadIdx.x; i < nd; i += blockDim.x) {
     const float v = lds_scores[i];
@@ -150,13 +148,7 @@ __global__ __launch_bounds__(256) void bm25_block_kernel(
   if ((threadIdx.x % WAVE) == 0 && zc)
     atomicAdd(&my[ZBIN], zc);
   __syncthreads();
-  unsigned* hrow = hist1 + (long)q * 256;
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) {
-    unsigned sum = 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) sum += lh[c * 264 + i];
-    if (sum) atomicAdd(&hrow[i], sum);
-  }
+  hist8_merge(lh, hist1 + (long)q * 256);
 }
 
 // Fused score-combine: out = wa * a + wb * b (optional linear hybrid;
@@ -190,7 +182,7 @@ extern "C" void infomesh_bm25_block(
   }
   dim3 grid((unsigned)B, (unsigned)nblocks);
   const size_t shm = (size_t)BD * sizeof(float)
-      + (hist1 ? 8 * 264 * sizeof(unsigned) : 0);
+      + (hist1 ? HIST8_U32 * sizeof(unsigned) : 0);
   if (hist1)
     hipLaunchKernelGGL(bm25_block_kernel<true>, grid, dim3(256), shm, s,
                        (const int*)doc_ids, (const unsigned int*)tfdl,

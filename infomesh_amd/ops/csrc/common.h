@@ -105,6 +105,33 @@ DEVINL float ordered_to_float(uint32_t u) {
   return __uint_as_float(v);
 }
 
+// 256-bin LDS histogram in 8 padded copies (topk.hip hist1_kernel,
+// bm25.hip fused hist1): a single 256-bin LDS histogram is
+// atomic-serialization bound (~2.1 TB/s measured). Copy c starts at
+// c*264 ints — 264 % 64 = 8, so the 8 copies of any bin land in 8
+// DISTINCT LDS banks, and lane L writing copy L&7 spreads a wave's
+// atomics across banks even when bins collide.
+constexpr int HIST8_COPIES = 8, HIST8_STRIDE = 264;
+constexpr int HIST8_U32 = HIST8_COPIES * HIST8_STRIDE;  // LDS footprint
+
+// Zero all copies; the caller barriers before the first hist8_mine add.
+DEVINL void hist8_zero(unsigned* lh) {
+  for (int i = threadIdx.x; i < HIST8_U32; i += blockDim.x) lh[i] = 0;
+}
+// This lane's copy.
+DEVINL unsigned* hist8_mine(unsigned* lh) {
+  return lh + (threadIdx.x & (HIST8_COPIES - 1)) * HIST8_STRIDE;
+}
+// Sum the copies into a global 256-bin row (after a barrier).
+DEVINL void hist8_merge(const unsigned* lh, unsigned* __restrict__ hrow) {
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) {
+    unsigned sum = 0;
+#pragma unroll
+    for (int c = 0; c < HIST8_COPIES; ++c) sum += lh[c * HIST8_STRIDE + i];
+    if (sum) atomicAdd(&hrow[i], sum);
+  }
+}
+
 // XCD-aware bijective blockIdx remap (guide §5.5 T1): contiguous chunks
 // per XCD so neighbouring tiles share an L2.
 DEVINL int xcd_swizzle(int bid, int nwg) {

@@ -270,101 +270,41 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
     return out
 
 
-# Workspace layout offsets (u32 units) — keep in sync with topk.hip:
-# hist1[B*256] | hist2[B*256] | bin1 | chi1 | thresh16 | cnt | cnt_eq
-# | overflow. Exposed as functions because the dense plane's
-# graph-replay path re-arms the deferred overflow check by hand (a
-# hardcoded copy of these offsets once went stale and read cnt_eq as
-# the overflow flag — round-2 fix).
-def topk_cnt_off(B: int) -> int:
-    return B * 512 + 3 * B
-
-
-def topk_flag_off(B: int) -> int:
-    return B * 512 + 5 * B
-
-
 class TopK:
-    """Reusable top-k selector (keeps its workspace allocated).
-
-    With defer_check=True the overflow flag is NOT read per call (a
-    host sync that would break stream overlap); the caller invokes
-    check_pending() after its next natural sync point."""
+    """Reusable top-k selector: keeps its workspace (histograms,
+    counters and the candidate buffer, sized by the extension)
+    allocated across calls, so a query plane pays no allocation per
+    batch. Asynchronous like every other wrapper: launches on the
+    current stream and returns without a host sync."""
 
     def __init__(self, device: torch.device | str = "cuda"):
         self.device = torch.device(device)
         self._ws: torch.Tensor | None = None
-        self._ws_b = 0
-        self.defer_check = False
-        self._pending: list[tuple[torch.Tensor, int]] = []
 
     def __call__(self, scores: torch.Tensor, k: int,
-                 sampled: bool | None = None,
                  ext_hist1: torch.Tensor | None = None
                  ) -> tuple[torch.Tensor, torch.Tensor]:
         assert scores.dim() == 2
         _check(scores, torch.float32, "scores")
         B, N = scores.shape
         assert 1 <= k <= 1024
-        if sampled is None:
-            # Default EXACT. The sampled threshold additionally assumes
-            # (a) a near-continuous score distribution (massively tied
-            # scores — e.g. BM25 tails — overflow the candidate cap) and
-            # (b) N <~ 2.7M: beyond that the sample stride makes the
-            # Gamma(Kp) candidate-count tails collide with the cap.
-            # Failures are loud (overflow/undershoot RuntimeError), and
-            # in-engine benchmarks showed no shape where it is a net
-            # win, so nothing auto-enables it.
-            sampled = False
-        lib = _ext.lib()
-        nu32 = lib.infomesh_topk_workspace_u32(B)
-        if self._ws is None or self._ws_b < nu32:
-            self._ws = torch.empty(nu32, device=scores.device,
-                                   dtype=torch.int32)
-            self._ws_b = nu32
-        self._ws[: B * 512 + 5 * B + 2].zero_()  # hists + counters region
-        vals = torch.empty((B, k), device=scores.device, dtype=torch.float32)
-        idx = torch.empty((B, k), device=scores.device, dtype=torch.int32)
         if ext_hist1 is not None:
-            # producer-fused pass 1 (bm25_block hist1=): exact counts,
-            # mutually exclusive with the sampled threshold
-            assert not sampled
+            # producer-fused pass 1 (bm25_block hist1=): exact counts
             assert ext_hist1.dtype == torch.int32 \
                 and ext_hist1.numel() >= B * 256
+        lib = _ext.lib()
+        nu32 = lib.infomesh_topk_workspace_u32(B)
+        if self._ws is None or self._ws.numel() < nu32:
+            self._ws = torch.empty(nu32, device=scores.device,
+                                   dtype=torch.int32)
+        self._ws[:lib.infomesh_topk_zero_u32(B)].zero_()
+        vals = torch.empty((B, k), device=scores.device, dtype=torch.float32)
+        idx = torch.empty((B, k), device=scores.device, dtype=torch.int32)
         lib.infomesh_topk(scores.data_ptr(), self._ws.data_ptr(),
                           vals.data_ptr(), idx.data_ptr(), B, N, k,
-                          int(sampled),
                           0 if ext_hist1 is None else ext_hist1.data_ptr(),
                           _ext.stream_ptr())
-        # cnt[B], cnt_eq[B], then the overflow flag after the histograms.
-        cnt_off = topk_cnt_off(B)
-        flag_off = topk_flag_off(B)
-        need = min(k, N) if sampled else 0
-        if self.defer_check:
-            self._pending.append((self._ws, cnt_off, flag_off, B, need))
-        else:
-            self._verify(self._ws, cnt_off, flag_off, B, need)
         return vals, idx
-
-    @staticmethod
-    def _verify(ws, cnt_off, flag_off, B, need) -> None:
-        if int(ws[flag_off].item()) != 0:
-            raise RuntimeError(
-                "topk strictly-above-threshold candidates exceeded the "
-                "reserve (an unlucky sampled threshold); rerun with "
-                "sampled=False")
-        if need:
-            # available candidates = strictly-above + threshold-equal
-            avail = ws[cnt_off:cnt_off + B] + ws[cnt_off + B:cnt_off + 2 * B]
-            if int(avail.min().item()) < need:
-                raise RuntimeError(
-                    "topk sampled threshold undershot (cnt < k); "
-                    "rerun with sampled=False")
-
-    def check_pending(self) -> None:
-        pending, self._pending = self._pending, []
-        for ws, cnt_off, flag_off, B, need in pending:
-            self._verify(ws, cnt_off, flag_off, B, need)
 
 
 def topk(scores: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
@@ -399,7 +339,8 @@ def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
     assert nblocks <= 65535 and qt_off.numel() == B + 1
     assert doc_ids.dtype == torch.int32 and tfdl.dtype == torch.int32
     assert bounds.numel() >= U * nblocks * 2
-    assert bd * 4 + (8 * 264 * 4 if hist1 is not None else 0) <= 160 * 1024
+    # 8448 B = HIST8_U32 (common.h) u32 histogram copies after the tile
+    assert bd * 4 + (8448 if hist1 is not None else 0) <= 160 * 1024
     if hist1 is not None:
         # fused topk pass 1: exact [B,256] ordered-top-byte counts of the
         # written score columns (caller zeroes it before the first

@@ -268,10 +268,6 @@ class DistributedQueryPlane:
         # view(int64) then raises. _as_i64 guarantees offset-0 storage.
         bm_i = _as_i64(g[:, :, 2 * k_:4 * k_])
         dn_i = _as_i64(g[:, :, 4 * k_:6 * k_])
-        for tk in (self.shard._get_topk(),
-                   getattr(self.shard, "_topk_dense", None)):
-            if tk is not None and getattr(tk, "defer_check", False):
-                tk.check_pending()
         tp = mark("plane.gather", tp)
         if self.fabric.rank != 0:
             return None
@@ -327,8 +323,7 @@ class DistributedQueryPlane:
             phase_t[name] = phase_t.get(name, 0.0) + (t1 - t0)
             return t1
         dev = self.shard.device
-        self.shard._get_topk().defer_check = True
-        self.shard._get_topk_dense().defer_check = True
+        self.shard.graph_dense = True
         if self._bm25_stream is None:
             self._bm25_stream = torch.cuda.Stream(dev)
         # terms must be broadcast before any rank's shard work

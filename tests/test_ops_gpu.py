@@ -666,28 +666,44 @@ def test_gemm8_n_chunked(monkeypatch):
     assert torch.equal(chunked, whole)
 
 
-def test_topk_sampled_vs_exact():
-    """Sampled threshold path (default at large N) == exact path."""
-    from infomesh_amd.ops.kernels import TopK
-    scores = torch.randn(4, 500_000, device="cuda")
-    t = TopK("cuda")
-    v1, i1 = t(scores, 100, sampled=True)
-    v2, i2 = t(scores, 100, sampled=False)
-    assert torch.allclose(v1, v2, atol=0)
-    rv, _ = torch.topk(scores, 100, dim=-1)
-    assert torch.allclose(v1, rv, atol=0)
-
-
-def test_topk_sampled_constant_scores_valid():
-    """Constant scores: every element ties the sampled threshold. The
+def test_topk_constant_scores_valid():
+    """Constant scores: every element ties the threshold. The
     tie-tolerant compact keeps a capped set of interchangeable
     candidates, so the result is a VALID top-k (it used to be a loud
     overflow error)."""
     from infomesh_amd.ops.kernels import TopK
     scores = torch.ones(1, 300_000, device="cuda")
     t = TopK("cuda")
-    v, i = t(scores, 10, sampled=True)
+    v, i = t(scores, 10)
     assert (v == 1.0).all() and len(set(i[0].tolist())) == 10
+
+
+def test_topk_producer_histogram_matches_own_pass1():
+    """ext_hist1 (the producer-fused pass 1) against the selector's own
+    hist1 pass. N = 20 011 is no multiple of 4 (scalar tails run) and
+    spans two grid chunks of 16 384; exact zeros and a negative block
+    exercise both branches of the ordered-float mapping. The 100th
+    value is untied here, so no tie is dropped and indices are
+    deterministic."""
+    from infomesh_amd.ops.kernels import TopK
+    g = torch.Generator().manual_seed(7)
+    host = torch.randn(3, 20_011, generator=g)
+    host[:, 5::97] = 0.0
+    host[:, 12_000:13_000] = -host[:, 12_000:13_000].abs() - 1.0
+    # float_to_ordered (common.h): negative -> ~bits, else bits | sign
+    bits = host.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    ordered = torch.where(bits >= 0x80000000, bits ^ 0xFFFFFFFF,
+                          bits | 0x80000000)
+    top = ordered >> 24
+    hist = torch.stack([torch.bincount(r, minlength=256) for r in top])
+    assert hist.shape == (3, 256) and int(hist.sum()) == host.numel()
+    scores = host.cuda()
+    v_ext, i_ext = TopK()(scores, 100,
+                          ext_hist1=hist.to(torch.int32).cuda())
+    v_own, i_own = TopK()(scores, 100)
+    assert torch.equal(v_ext, v_own) and torch.equal(i_ext, i_own)
+    rv, _ = torch.topk(scores, 100, dim=-1)
+    assert torch.equal(v_own, rv)
 
 
 @pytest.mark.gpu
