@@ -85,6 +85,9 @@ class GpuConfig:
     dtype: str = "bf16"
     topk_per_shard: int = 100
     require_extension: bool = True     # GPU present but ext missing → hard error
+    # site:/lang:/after:/before: queries run on the GPU plane (masked
+    # top-k) instead of the FTS5 path
+    filters: bool = False
 
 
 @dataclass(frozen=True)

@@ -12,12 +12,15 @@ is testable without a GPU and the GPU path is identical code.
 from __future__ import annotations
 
 import logging
+import time
 
 import numpy as np
 import torch
 
+from .index.doc_attrs import DocFilter, pack_attrs
 from .index.gpu_index import CpuShard, GpuShard, bm25_term_ids
-from .index.local_store import Document, LocalStore, SearchHit
+from .index.local_store import (Document, LocalStore, SearchHit,
+                                extract_domain)
 from .parallel.fabric import Fabric
 from .parallel.query_plane import DistributedQueryPlane
 
@@ -60,6 +63,7 @@ class HybridEngine:
         self._pending_tokens: list[np.ndarray] = []
         self._pending_texts: list[str] = []
         self._pending_ids: list[int] = []
+        self._pending_attrs: list[tuple] = []
         # (embeddings and postings of already-built docs live in the
         # shard itself: flush merges rather than re-accumulating, so
         # engine memory does not grow with corpus size)
@@ -73,6 +77,26 @@ class HybridEngine:
         # vector_store.py:144-157 truncates at 2000 chars)
         self._pending_texts.append(text[:self.embed_max_chars])
         self._pending_ids.append(doc.doc_id)
+        # filter attributes (site:/lang:/after:/before: on the GPU plane)
+        self._pending_attrs.append(pack_attrs(
+            doc.language, doc.domain or extract_domain(doc.url),
+            doc.crawled_at or time.time()))
+
+    def delete_documents(self, doc_ids) -> int:
+        """Forget documents at once, with no flush: pending entries are
+        dropped and built rows are tombstoned in the shard (the masked
+        top-k never returns them). Returns how many entries went."""
+        gone = {int(d) for d in doc_ids}
+        if not gone:
+            return 0
+        keep = [i for i, d in enumerate(self._pending_ids) if d not in gone]
+        n = len(self._pending_ids) - len(keep)
+        if n:
+            self._pending_tokens = [self._pending_tokens[i] for i in keep]
+            self._pending_texts = [self._pending_texts[i] for i in keep]
+            self._pending_ids = [self._pending_ids[i] for i in keep]
+            self._pending_attrs = [self._pending_attrs[i] for i in keep]
+        return n + self.shard.delete(gone)
 
     @property
     def pending_count(self) -> int:
@@ -125,8 +149,14 @@ class HybridEngine:
 
         tokens = self._pending_tokens
         ids = self._pending_ids
+        attrs = self._pending_attrs
         self._pending_tokens, self._pending_texts, self._pending_ids = \
             [], [], []
+        self._pending_attrs = []
+        # a recrawl keeps its doc id: tombstone the built row it
+        # replaces, so the stale text stops ranking and the id appears
+        # once (an id pending twice keeps both rows until the next one)
+        self.shard.delete(ids)
         if self.shard.n_docs == 0:
             lens = np.array([max(len(t), 1) for t in tokens],
                             dtype=np.int64)
@@ -139,12 +169,13 @@ class HybridEngine:
                      if self.gpu else CpuShard(emb_dtype=self.emb_dtype))
             shard.build_from_arrays(
                 flat_terms, flat_docs, lens,
-                np.asarray(ids, dtype=np.int64), new_emb)
+                np.asarray(ids, dtype=np.int64), new_emb, attrs=attrs)
         else:
             # epoch flip via segment merge: only the NEW docs are
             # tokenized/encoded; readers keep the old shard until the
             # merged one is fully installed
-            shard = self.shard.merged_with(tokens, ids, new_emb)
+            shard = self.shard.merged_with(tokens, ids, new_emb,
+                                           attrs=attrs)
         self.shard = shard
         self.plane.shard = shard
         log.info("engine flush: %d new docs, %d total, %.1f MB HBM",
@@ -153,17 +184,23 @@ class HybridEngine:
 
     # ------------------------------------------------------------ search
     def search(self, query: str, limit: int = 10,
-               use_dense: bool | None = None) -> list[SearchHit]:
+               use_dense: bool | None = None,
+               filter: DocFilter | None = None) -> list[SearchHit]:
         """Single-query search against the engine (shard-fused)."""
-        return self.search_many([query], limit=limit,
-                                use_dense=use_dense)[0]
+        return self.search_many(
+            [query], limit=limit, use_dense=use_dense,
+            filters=None if filter is None else [filter])[0]
 
     def search_many(self, queries: list[str], limit: int = 10,
-                    use_dense: bool | None = None) -> list[list[SearchHit]]:
+                    use_dense: bool | None = None,
+                    filters: list[DocFilter | None] | None = None
+                    ) -> list[list[SearchHit]]:
         """Batched search: ONE collective plane.search_batch for the
         whole list (the batcher's execute path). Fusion happens exactly
         once, on the plane (RRF of the per-shard BM25 + dense top-k);
-        callers hydrate url/title from the LocalStore."""
+        callers hydrate url/title from the LocalStore. filters: one
+        DocFilter or None per query, applied inside the shards' top-k
+        selection."""
         if self.shard.n_docs == 0 or not queries:
             return [[] for _ in queries]
         B = len(queries)
@@ -181,9 +218,14 @@ class HybridEngine:
         if use_dense and self.encoder is not None:
             texts = queries + [""] * (Bp - B)
             emb = self.encoder.encode_texts(texts)
+        if filters is not None:
+            assert len(filters) == B, "one filter (or None) per query"
+            filters = (list(filters) + [None] * (Bp - B)
+                       if any(f is not None for f in filters) else None)
         fused = self.plane.search_batch(
             terms, emb, B=Bp, dim=emb.shape[1] if emb is not None else 384,
-            n_results=limit, use_dense=use_dense and emb is not None)
+            n_results=limit, use_dense=use_dense and emb is not None,
+            filters=filters)
         if fused is None:
             return [[] for _ in queries]
         ids = fused.ids.tolist()
@@ -206,6 +248,7 @@ class HybridEngine:
             "device": self.device,
             "docs_indexed": self.shard.n_docs,
             "docs_pending": self.pending_count,
+            "docs_dead": self.shard.n_dead,
             "hbm_bytes": self.shard.hbm_bytes(),
             "world_size": self.fabric.world,
             "encoder": self.encoder is not None,

@@ -1,0 +1,106 @@
+"""Per-document filter attributes and query predicates, as packed words.
+
+The one Python packer for the 16-byte attribute record and the 16-byte
+predicate that the GPU filter kernel reads; the layout itself is written
+down once, in the header of ops/csrc/docfilter.hip. Replaces on the GPU
+plane: the reference's SQL filters on the documents table
+(infomesh/index/local_store.py, language/domain/crawled_at columns).
+
+Words are unsigned 32-bit values; tensors carry them as int32 with the
+same bits (torch has no uint32 arithmetic worth relying on).
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from ..hashing import hash64
+
+LANG_MASK = 0xFFFF
+DEAD_BIT = 1 << 16      # attribute word 1
+HAS_SITE_BIT = 1 << 16  # predicate word z
+U32_MAX = 0xFFFFFFFF
+
+
+def lang16(language: str | None) -> int:
+    """ord(c0)<<8 | ord(c1) of the lower-cased 2-letter code; 0 for
+    unknown (None, empty, or not two ASCII characters)."""
+    code = (language or "").strip().lower()[:2]
+    if len(code) != 2 or not code.isascii():
+        return 0
+    return (ord(code[0]) << 8) | ord(code[1])
+
+
+def domain_hash(domain: str | None) -> int:
+    """Low 32 bits of hash64 of the lower-cased domain, as
+    `extract_domain` / LocalStore store it."""
+    return hash64((domain or "").strip().lower()) & U32_MAX
+
+
+def _clamp_u32(v: float) -> int:
+    return int(min(max(v, 0), U32_MAX))
+
+
+def pack_attrs(language: str | None, domain: str | None,
+               crawled_at: float | None) -> tuple[int, int, int, int]:
+    """One document's attribute words (w0, w1, w2, w3). `crawled_at` is
+    truncated to whole seconds. The dead bit is never set here; only
+    `GpuShard.delete` sets it."""
+    return (_clamp_u32(math.floor(crawled_at or 0.0)), lang16(language),
+            domain_hash(domain), 0)
+
+
+@dataclass(frozen=True)
+class DocFilter:
+    """A query's metadata restriction; every None field is unrestricted.
+
+    Date bounds compare WHOLE seconds on the GPU plane: `after` is
+    rounded up and `before` is rounded down, then a document passes iff
+    after <= floor(crawled_at) <= before. SQLite compares the REAL
+    column, so the two planes can differ for a document crawled within
+    the same second as a fractional bound."""
+    language: str | None = None
+    site: str | None = None
+    after: float | None = None
+    before: float | None = None
+
+
+def pack_pred(f) -> tuple[int, int, int, int]:
+    """Predicate words (x, y, z, w) of a DocFilter; None is the
+    live-only predicate. A 4-tuple is taken as words already packed
+    (the query plane forwards predicates between ranks in that form)."""
+    if f is None:
+        return (0, U32_MAX, 0, 0)
+    if isinstance(f, tuple):
+        x, y, z, w = (int(v) & U32_MAX for v in f)
+        return (x, y, z, w)
+    x = 0 if f.after is None else _clamp_u32(math.ceil(f.after))
+    y = U32_MAX if f.before is None else _clamp_u32(math.floor(f.before))
+    z = lang16(f.language)
+    w = 0
+    if f.site:
+        z |= HAS_SITE_BIT
+        w = domain_hash(f.site)
+    return (x, y, z, w)
+
+
+def words_i32(rows) -> np.ndarray:
+    """[n, 4] u32 words -> the int32 array with the same bits."""
+    return np.asarray(rows, dtype=np.uint32).reshape(-1, 4).view(np.int32)
+
+
+def passes(attrs: np.ndarray, pred) -> np.ndarray:
+    """The predicate in numpy: attrs [N, 4] (int32 or uint32 bits), pred
+    4 words -> bool [N]. CpuShard and the bitmask oracle both use it."""
+    a = np.ascontiguousarray(attrs).view(np.uint32).reshape(-1, 4)
+    x, y, z, w = (int(v) & U32_MAX for v in pred)
+    qlang = z & LANG_MASK
+    ok = (a[:, 1] & np.uint32(DEAD_BIT)) == 0
+    ok &= (a[:, 0] >= np.uint32(x)) & (a[:, 0] <= np.uint32(y))
+    if qlang:
+        ok &= (a[:, 1] & np.uint32(LANG_MASK)) == np.uint32(qlang)
+    if z & HAS_SITE_BIT:
+        ok &= a[:, 2] == np.uint32(w)
+    return ok

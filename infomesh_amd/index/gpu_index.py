@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from ..hashing import hash64
+from .doc_attrs import DEAD_BIT, DocFilter, pack_pred, passes, words_i32
 
 BM25_K1 = 1.2
 BM25_B = 0.75
@@ -126,6 +127,11 @@ class GpuShard:
         # dense plane: capacity-growth device buffers ([:n_docs] live)
         self._emb_buf: torch.Tensor | None = None   # [cap, D] bf16 (unit)
         self._gid_buf: torch.Tensor | None = None   # [cap] i64
+        # filter attributes, one 16-byte record per doc (doc_attrs.py);
+        # bit 16 of word 1 is the tombstone set by delete()
+        self._attr_buf: torch.Tensor | None = None  # [cap, 4] i32
+        self.n_dead = 0
+        self._live_bits = None   # cached live-only mask (+ ready event)
         self._topk = None
         self._topk_dense = None
         self._dense_graphs: dict = {}
@@ -138,6 +144,7 @@ class GpuShard:
         self._pend_tokens: list[np.ndarray] = []
         self._pend_emb: list[torch.Tensor] = []
         self._pend_gids: list[int] = []
+        self._pend_attrs: list = []
 
     # ------------------------------------------------- derived views
     @property
@@ -153,6 +160,12 @@ class GpuShard:
         return self._gid_buf[:self.n_docs]
 
     @property
+    def attrs(self) -> torch.Tensor | None:
+        if self._attr_buf is None:
+            return None
+        return self._attr_buf[:self.n_docs]
+
+    @property
     def doc_norm(self) -> torch.Tensor:
         """BM25 length norm per doc (host-derived; kernels compute this
         in-flight from packed dl — kept for the CPU oracle/tests)."""
@@ -162,9 +175,13 @@ class GpuShard:
 
     # ------------------------------------------------------------ build
     def add_document(self, global_id: int, term_ids: np.ndarray,
-                     embedding: torch.Tensor | None) -> None:
+                     embedding: torch.Tensor | None,
+                     attrs=None) -> None:
+        """attrs: the 4 words of doc_attrs.pack_attrs, or None for an
+        all-zero record (no language, no date, no domain)."""
         self._pend_tokens.append(term_ids.astype(np.int64))
         self._pend_gids.append(global_id)
+        self._pend_attrs.append(attrs)
         if embedding is not None:
             self._pend_emb.append(embedding.reshape(1, -1))
 
@@ -178,20 +195,25 @@ class GpuShard:
         token_lists = self._pend_tokens
         gids = list(self._pend_gids)
         embs = self._pend_emb
+        attrs = self._pend_attrs
         self._pend_tokens, self._pend_gids, self._pend_emb = [], [], []
+        self._pend_attrs = []
         new_emb = torch.cat(embs, 0) if embs else None
-        self._append_segment(token_lists, gids, new_emb)
+        self._append_segment(token_lists, gids, new_emb, attrs=attrs)
         if len(self.segments) > MAX_SEGMENTS:
             self.optimize()
 
     def merged_with(self, token_lists: list[np.ndarray],
                     gids: list[int],
-                    new_emb: torch.Tensor | None) -> "GpuShard":
+                    new_emb: torch.Tensor | None,
+                    attrs=None) -> "GpuShard":
         """Return a NEW shard = this shard + the given docs, sharing
         the immutable segments/buffers with this one (epoch-flip:
         readers of the old shard never see the new docs because every
         read is bounded by the old n_docs). Linear use only — append to
-        the RETURNED shard, not to this one, afterwards."""
+        the RETURNED shard, not to this one, afterwards. The attribute
+        buffer is shared too, so a delete() on either shard tombstones
+        the common rows for both at once."""
         out = type(self)() if type(self).__init__ is not GpuShard.__init__ \
             else GpuShard(str(self.device), vocab=self.vocab,
                           emb_dtype=self.emb_dtype)
@@ -204,11 +226,14 @@ class GpuShard:
         out.avgdl = self.avgdl
         out._emb_buf = self._emb_buf
         out._gid_buf = self._gid_buf
-        out._append_segment(token_lists, gids, new_emb)
+        out._attr_buf = self._attr_buf
+        out.n_dead = self.n_dead
+        out._append_segment(token_lists, gids, new_emb, attrs=attrs)
         return out
 
     def _append_segment(self, token_lists: list[np.ndarray],
-                        gids: list, new_emb: torch.Tensor | None) -> None:
+                        gids: list, new_emb: torch.Tensor | None,
+                        attrs=None) -> None:
         lens2 = np.array([max(len(t), 1) for t in token_lists],
                          dtype=np.int64)
         flat_terms = (np.concatenate(
@@ -218,18 +243,39 @@ class GpuShard:
         flat_docs = np.repeat(np.arange(len(token_lists), dtype=np.int64),
                               [len(t) for t in token_lists])
         self._install_segment(flat_terms, flat_docs, lens2,
-                              np.asarray(gids, dtype=np.int64), new_emb)
+                              np.asarray(gids, dtype=np.int64), new_emb,
+                              attrs)
 
     def build_from_arrays(self, flat_terms: np.ndarray,
                           flat_docs: np.ndarray, doc_lens: np.ndarray,
                           global_ids: np.ndarray,
-                          embeddings: torch.Tensor | None) -> None:
+                          embeddings: torch.Tensor | None,
+                          attrs=None) -> None:
         """Bulk build from flat (term, doc-local-id) pairs — installs a
         single segment (doc ids must be 0..len(doc_lens)-1)."""
         self._install_segment(flat_terms, flat_docs,
                               np.asarray(doc_lens, dtype=np.int64),
                               np.asarray(global_ids, dtype=np.int64),
-                              embeddings)
+                              embeddings, attrs)
+
+    @staticmethod
+    def _attr_rows(attrs, n: int) -> np.ndarray | None:
+        """attrs argument -> [n, 4] int32 words, or None when every
+        record is all-zero. Accepts an [n, 4] array or a list whose
+        entries are 4 words or None."""
+        if attrs is None:
+            return None
+        if isinstance(attrs, np.ndarray):
+            rows = attrs.reshape(-1, 4)
+            rows = (rows.view(np.int32) if rows.dtype.itemsize == 4
+                    else words_i32(rows))
+        else:
+            if all(a is None for a in attrs):
+                return None
+            rows = words_i32([a if a is not None else (0, 0, 0, 0)
+                              for a in attrs])
+        assert rows.shape == (n, 4), "one attribute record per document"
+        return rows
 
     @staticmethod
     def _aggregate(flat_terms: np.ndarray, flat_docs: np.ndarray,
@@ -273,7 +319,8 @@ class GpuShard:
     def _install_segment(self, flat_terms: np.ndarray,
                          flat_docs: np.ndarray, doc_lens: np.ndarray,
                          global_ids: np.ndarray,
-                         embeddings: torch.Tensor | None) -> None:
+                         embeddings: torch.Tensor | None,
+                         attrs=None) -> None:
         n_new = len(doc_lens)
         if n_new == 0:
             return
@@ -314,6 +361,21 @@ class GpuShard:
         need = self.n_docs + n_new
         self._gid_buf = self._grow(self._gid_buf, need, (), torch.int64)
         gid_t = self._upload(global_ids.astype(np.int64), stream)
+        self._attr_buf = self._grow(self._attr_buf, need, (4,), torch.int32)
+        attr_rows = self._attr_rows(attrs, n_new)
+        attr_t = (self._upload(attr_rows, stream)
+                  if attr_rows is not None else None)
+
+        def put_attrs():
+            if attr_t is None:
+                self._attr_buf[self.n_docs:need].zero_()
+            else:
+                self._attr_buf[self.n_docs:need].copy_(attr_t)
+        if stream is not None:
+            with torch.cuda.stream(stream):
+                put_attrs()
+        else:
+            put_attrs()
         if embeddings is not None:
             e = embeddings
             store_dtype = (torch.float8_e4m3fn if self.emb_dtype == "fp8"
@@ -394,6 +456,7 @@ class GpuShard:
         self._dense_graphs = {}
         self._dense_bufs = {}
         self._bm25_hists = {}
+        self._live_bits = None
 
     def optimize(self) -> None:
         """Merge all posting segments into one, entirely on-device:
@@ -428,9 +491,123 @@ class GpuShard:
             h_offs=offsets.cpu().numpy())]
         self._invalidate_query_caches()
 
+    # ---------------------------------------------------------- deletes
+    def delete(self, global_ids) -> int:
+        """Tombstone every row whose global id is in `global_ids`;
+        returns how many rows were newly marked dead. One O(N) device
+        `isin` — deletes are rare, so no host id map that grows with
+        the corpus. The attribute buffer is shared between epochs
+        (merged_with), so a delete shows at once, without a flush.
+
+        Tombstoned rows keep counting in `df`, `avgdl` and `n_docs`
+        (hence in every idf) until purge() — the Lucene convention:
+        scores of live documents do not move when a neighbour dies."""
+        ids = np.unique(np.asarray(list(global_ids), dtype=np.int64))
+        if self.n_docs == 0 or ids.size == 0:
+            return 0
+        w1 = self._attr_buf[:self.n_docs, 1]
+        hit = torch.isin(self.global_ids, torch.from_numpy(ids).to(self.device))
+        hit &= (w1 & DEAD_BIT) == 0
+        n = int(hit.sum())
+        if n:
+            w1 |= hit.to(torch.int32) * DEAD_BIT
+            self.n_dead += n
+            self._live_bits = None
+        return n
+
+    def purge(self) -> int:
+        """Physically drop tombstoned rows, on the shard's device (as
+        optimize() merges there): rebuild (term, doc, tfdl) from the
+        segments keeping live docs, renumber them densely, recompute
+        df / doc lengths / avgdl, compact the embedding, id and
+        attribute buffers and install ONE segment. Afterwards the shard
+        equals one bulk-built from the survivors. Returns the number of
+        rows dropped."""
+        if self.n_dead == 0:
+            return 0
+        dev, V, n_old = self.device, self.vocab, self.n_docs
+        live = (self._attr_buf[:n_old, 1] & DEAD_BIT) == 0
+        new_id = torch.cumsum(live, 0) - 1
+        keep_rows = live.nonzero().squeeze(1)
+        n_new = int(keep_rows.numel())
+        term_parts, doc_parts, tfdl_parts = [], [], []
+        arangeV = torch.arange(V, dtype=torch.int64, device=dev)
+        for seg in self.segments:
+            term_parts.append(
+                torch.repeat_interleave(arangeV, seg.offsets.diff()))
+            doc_parts.append(seg.doc_ids.to(torch.int64) + seg.doc_base)
+            tfdl_parts.append(seg.tfdl)
+        terms, docs = torch.cat(term_parts), torch.cat(doc_parts)
+        tfdl = torch.cat(tfdl_parts)
+        keep = live[docs]
+        terms, docs, tfdl = terms[keep], new_id[docs[keep]], tfdl[keep]
+        key, order = torch.sort(terms * max(n_new, 1) + docs)
+        df_dev = torch.bincount(terms, minlength=V)
+        offsets = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(df_dev, 0, out=offsets[1:])
+        dropped = n_old - n_new
+        self.df = df_dev.cpu().numpy().astype(np.int64)
+        self._doc_lens = self._doc_lens[live.cpu().numpy()]
+        self.avgdl = float(self._doc_lens.mean()) if n_new else 1.0
+        self._gid_buf = self._gid_buf.index_select(0, keep_rows)
+        self._attr_buf = self._attr_buf.index_select(0, keep_rows)
+        if self._emb_buf is not None:
+            self._emb_buf = self._emb_buf.index_select(0, keep_rows)
+        self.n_docs = n_new
+        self.n_dead = 0
+        self.segments = [PostingSegment(
+            offsets=offsets,
+            doc_ids=(key % max(n_new, 1)).to(torch.int32),
+            tfdl=tfdl[order].contiguous(), doc_base=0, n_docs=n_new,
+            h_offs=offsets.cpu().numpy())] if n_new else []
+        self._invalidate_query_caches()
+        return dropped
+
+    # ---------------------------------------------------------- filters
+    def _pred_rows(self, filters, B: int):
+        """None when the mask is inactive (no filter in the batch and
+        no tombstone in the shard), else (preds [P, 4] i32 host words,
+        row_pred [B] host i32) with the batch's predicates deduped;
+        a None filter is the live-only predicate."""
+        if self.n_dead == 0 and (filters is None
+                                 or all(f is None for f in filters)):
+            return None
+        if filters is None:
+            filters = [None] * B
+        assert len(filters) == B, "one filter (or None) per query"
+        seen: dict = {}
+        rows = [seen.setdefault(pack_pred(f), len(seen)) for f in filters]
+        return words_i32(list(seen)), np.asarray(rows, dtype=np.int32)
+
+    def _mask_for(self, filters: list[DocFilter | None] | None, B: int):
+        """(bits [P, W] i32, row_pred [B] i32) on the device for the
+        masked top-k, or None when the mask is inactive."""
+        from ..ops import kernels as K
+        pr = self._pred_rows(filters, B)
+        if pr is None:
+            return None
+        preds, rows = pr
+        cur = torch.cuda.current_stream(self.device)
+        live_only = len(preds) == 1 and tuple(
+            preds.view(np.uint32)[0]) == pack_pred(None)
+        if live_only and self._live_bits is not None:
+            # cached until the next append or delete; the planes run on
+            # different streams, so order this one after the producer
+            bits, ready = self._live_bits
+            cur.wait_event(ready)
+            bits.record_stream(cur)
+        else:
+            bits = K.filter_bitmask(
+                self.attrs, torch.from_numpy(preds).to(self.device))
+            if live_only:
+                ready = torch.cuda.Event()
+                ready.record(cur)
+                self._live_bits = (bits, ready)
+        return bits, torch.from_numpy(rows).to(self.device)
+
     def hbm_bytes(self) -> int:
         total = sum(s.hbm_bytes() for s in self.segments)
-        for t in (self._emb_buf, self._gid_buf):
+        for t in (self._emb_buf, self._gid_buf, self._attr_buf):
             if t is not None:
                 total += t.numel() * t.element_size()
         return total
@@ -532,11 +709,17 @@ class GpuShard:
 
     def search_bm25(self, queries_terms: list[np.ndarray], k: int,
                     scores_buf: torch.Tensor | None = None,
-                    mark=None) -> tuple[torch.Tensor, torch.Tensor]:
+                    mark=None, filters=None, _mask=None
+                    ) -> tuple[torch.Tensor, torch.Tensor]:
         """BM25 plane only (needs terms, not embeddings) — callable on a
         side stream to overlap with query encoding. One kernel launch
         per posting segment; the segments' disjoint doc ranges cover
-        every column of the score matrix exactly once."""
+        every column of the score matrix exactly once.
+
+        filters: one DocFilter or None per query. With a filter in the
+        batch or a tombstone in the shard the select is masked: the
+        fused pass-1 histogram counts failing documents, so it is not
+        produced and the masked top-k streams the matrix once more."""
         import time as _time
         from ..ops import kernels as K
         if mark is None:
@@ -547,6 +730,7 @@ class GpuShard:
         N = self.n_docs
         k = min(k, N)
         topk = self._get_topk()
+        mask = _mask if _mask is not None else self._mask_for(filters, B)
         tp = _time.perf_counter()
         if scores_buf is not None and scores_buf.shape == (B, N):
             scores = scores_buf
@@ -590,13 +774,17 @@ class GpuShard:
                 self._h2d(f"qb{si}", seg.h_offs[uterms], torch.int64),
                 self._h2d(f"qe{si}", seg.h_offs[uterms + 1], torch.int64),
                 bounds, scores, seg.doc_base, seg.n_docs, bd,
-                self.avgdl, k1=BM25_K1, b=BM25_B, hist1=hist)
+                self.avgdl, k1=BM25_K1, b=BM25_B,
+                hist1=hist if mask is None else None)
         if dev.type == "cuda":
             if evt is None:
                 evt = self._h2d_evt = torch.cuda.Event()
             evt.record()
         tp = mark("shard.bm25", tp)
-        out = topk(scores, k, ext_hist1=hist)
+        if mask is None:
+            out = topk(scores, k, ext_hist1=hist)
+        else:
+            out = topk(scores, k, mask=mask[0], row_pred=mask[1])
         mark("shard.bm25topk", tp)
         self._bm25_scores_buf = scores
         return out
@@ -604,10 +792,15 @@ class GpuShard:
     def search(self, queries_terms: list[np.ndarray],
                query_emb: torch.Tensor | None, k: int = 100,
                scores_buf: torch.Tensor | None = None,
-               phase_t: dict | None = None) -> ShardHits:
+               phase_t: dict | None = None,
+               filters: list[DocFilter | None] | None = None
+               ) -> ShardHits:
         """Score all queries against this shard; returns fixed-size
         top-k with global ids (the per-peer result cap analogue,
-        reference p2p/routing.py:48)."""
+        reference p2p/routing.py:48). filters: one DocFilter or None per
+        query; filtered-out and deleted documents are never returned,
+        and a row with fewer than k passing documents pads with
+        -inf / id -1."""
         import time as _time
 
         def mark(name, t0):
@@ -624,14 +817,16 @@ class GpuShard:
         assert N > 0, "shard is empty"
         k = min(k, N)
         tp = _time.perf_counter()
+        mask = self._mask_for(filters, B)   # once for both planes
         bm_vals, bm_idx = self.search_bm25(queries_terms, k,
                                            scores_buf=scores_buf,
-                                           mark=mark)
+                                           mark=mark, _mask=mask)
         tp = _time.perf_counter()
 
         # --- dense plane ---
         if query_emb is not None and self.embeddings is not None:
-            dn_vals, dn_idx = self.search_dense(query_emb, k, mark=mark)
+            dn_vals, dn_idx = self.search_dense(query_emb, k, mark=mark,
+                                                _mask=mask)
         else:
             dn_vals = torch.full((B, k), -float("inf"), device=dev)
             dn_idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
@@ -642,8 +837,10 @@ class GpuShard:
                          dense_ids=self.to_global(dn_idx))
 
     def search_dense(self, query_emb: torch.Tensor, k: int,
-                     mark=None) -> tuple[torch.Tensor, torch.Tensor]:
-        """Dense (cosine) plane; runs after the query embedding exists."""
+                     mark=None, filters=None, _mask=None
+                     ) -> tuple[torch.Tensor, torch.Tensor]:
+        """Dense (cosine) plane; runs after the query embedding exists.
+        filters: as in search_bm25."""
         import time as _time
         from ..ops import kernels as K
         if mark is None:
@@ -652,13 +849,16 @@ class GpuShard:
         B = query_emb.shape[0]
         N = self.n_docs
         k = min(k, N)
+        mask = _mask if _mask is not None else self._mask_for(filters, B)
         tp = _time.perf_counter()
         emb = self.embeddings
         # hipGraph capture of the whole plane (GEMM + top-k passes, all
         # fixed shapes) removes ~10 launch gaps per batch. Opt-in per
         # shard (graph_dense). Graphs are invalidated on every append
         # (the captured embeddings view goes stale).
-        if self.device.type == "cuda" and self.graph_dense:
+        # A masked batch runs uncaptured: its mask and row_pred tensors
+        # change per batch, which a captured graph cannot follow.
+        if self.device.type == "cuda" and self.graph_dense and mask is None:
             g = self._dense_graphs.get((B, k))
             if g is None:
                 from ..ops.graphs import GraphedCallable
@@ -677,7 +877,11 @@ class GpuShard:
             return out
         d_scores = self._dense_gemm(query_emb, emb, B, N)
         tp = mark("shard.dense", tp)
-        out = self._get_topk_dense()(d_scores, k)
+        if mask is None:
+            out = self._get_topk_dense()(d_scores, k)
+        else:
+            out = self._get_topk_dense()(d_scores, k, mask=mask[0],
+                                         row_pred=mask[1])
         mark("shard.densetopk", tp)
         return out
 
@@ -736,8 +940,30 @@ class CpuShard(GpuShard):
     def __init__(self, vocab: int = BM25_VOCAB, emb_dtype: str = "bf16"):
         super().__init__(device="cpu", vocab=vocab, emb_dtype=emb_dtype)
 
+    def _fail_rows(self, filters, B: int) -> torch.Tensor | None:
+        """bool [B, N], True where a document fails its row's predicate
+        (the same packed words the GPU kernel reads); None when the
+        mask is inactive."""
+        pr = self._pred_rows(filters, B)
+        if pr is None:
+            return None
+        preds, rows = pr
+        a = self.attrs.numpy()
+        ok = np.stack([passes(a, p) for p in preds.view(np.uint32)])
+        return torch.from_numpy(~ok[rows])
+
+    @staticmethod
+    def _masked_topk(scores: torch.Tensor, fail: torch.Tensor | None,
+                     k: int) -> tuple[torch.Tensor, torch.Tensor]:
+        if fail is None:
+            return torch.topk(scores, k, dim=1)
+        vals, idx = torch.topk(
+            scores.masked_fill(fail, -float("inf")), k, dim=1)
+        return vals, torch.where(vals == -float("inf"),
+                                 torch.full_like(idx, -1), idx)
+
     def search(self, queries_terms, query_emb, k: int = 100,
-               scores_buf=None, phase_t=None) -> ShardHits:
+               scores_buf=None, phase_t=None, filters=None) -> ShardHits:
         B = len(queries_terms)
         N = self.n_docs
         assert N > 0, "shard is empty"
@@ -761,10 +987,11 @@ class CpuShard(GpuShard):
                     scores[qi, d] += (idf * tf * (BM25_K1 + 1)
                                       / (tf + norm[d]))
         st = torch.from_numpy(scores)
-        bm_vals, bm_idx = torch.topk(st, k, dim=1)
+        fail = self._fail_rows(filters, B)
+        bm_vals, bm_idx = self._masked_topk(st, fail, k)
         if query_emb is not None and self.embeddings is not None:
             d_scores = query_emb.float().cpu() @ self.embeddings.float().T
-            dn_vals, dn_idx = torch.topk(d_scores, k, dim=1)
+            dn_vals, dn_idx = self._masked_topk(d_scores, fail, k)
         else:
             dn_vals = torch.full((B, k), -float("inf"))
             dn_idx = torch.full((B, k), -1, dtype=torch.int64)

@@ -207,6 +207,15 @@ class LocalStore:
         self.conn.commit()
         return int(cur.lastrowid)
 
+    def doc_ids_where(self, column: str, value: str) -> list[int]:
+        """Ids of the rows a delete_by_* call would remove — collected
+        BEFORE the delete so the GPU engine can forget them too."""
+        assert column in ("url", "domain", "text_hash")
+        if column == "domain":
+            value = value.lower()
+        return [int(r["id"]) for r in self.conn.execute(
+            f"SELECT id FROM documents WHERE {column}=?", (value,))]
+
     def delete_document(self, doc_id: int) -> bool:
         cur = self.conn.execute("DELETE FROM documents WHERE id=?", (doc_id,))
         self.conn.commit()

@@ -8,6 +8,10 @@ load_shard re-uploads them to HBM without re-tokenizing/re-embedding.
 v2: segmented postings (offsets/doc_ids/tfdl per segment) + host doc
 lengths, matching gpu_index.PostingSegment — doc_lens persistence means
 incremental appends after a warm start work (round-1 ADVICE fix).
+
+The per-document filter attributes (doc_attrs.py, tombstones included)
+ride along as an optional tensor of the same version: a manifest written
+before they existed loads with all-zero records.
 """
 from __future__ import annotations
 
@@ -19,6 +23,7 @@ import numpy as np
 import torch
 
 from ..hashing import content_hash
+from .doc_attrs import DEAD_BIT
 from .gpu_index import CpuShard, GpuShard, PostingSegment
 
 MANIFEST_VERSION = 2
@@ -40,6 +45,8 @@ def save_shard(shard: GpuShard, path: str | Path, rank: int = 0,
         payload["global_ids"] = shard.global_ids.cpu()
     if shard.embeddings is not None:
         payload["embeddings"] = shard.embeddings.cpu()
+    if shard.attrs is not None:
+        payload["attrs"] = shard.attrs.cpu()
     meta = {
         "version": MANIFEST_VERSION,
         "tokenizer_version": TOKENIZER_VERSION,
@@ -92,6 +99,13 @@ def load_shard(path: str | Path, device: str = "cuda") -> GpuShard:
     emb = blob.get("embeddings")
     if emb is not None:
         shard._emb_buf = emb.to(dev).contiguous()
+    attrs = blob.get("attrs")
+    if attrs is not None:
+        shard._attr_buf = attrs.to(dev).contiguous()
+        shard.n_dead = int(((attrs[:, 1] & DEAD_BIT) != 0).sum())
+    elif shard.n_docs:
+        shard._attr_buf = torch.zeros((shard.n_docs, 4), device=dev,
+                                      dtype=torch.int32)
     return shard
 
 

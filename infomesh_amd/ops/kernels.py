@@ -282,12 +282,26 @@ class TopK:
         self._ws: torch.Tensor | None = None
 
     def __call__(self, scores: torch.Tensor, k: int,
-                 ext_hist1: torch.Tensor | None = None
+                 ext_hist1: torch.Tensor | None = None,
+                 mask: torch.Tensor | None = None,
+                 row_pred: torch.Tensor | None = None
                  ) -> tuple[torch.Tensor, torch.Tensor]:
+        """mask [P, W] i32 (filter_bitmask) + row_pred [B] i32 select
+        among passing documents only: row b honours mask[row_pred[b]];
+        rows with fewer than k passing documents pad with -inf / -1."""
         assert scores.dim() == 2
         _check(scores, torch.float32, "scores")
         B, N = scores.shape
         assert 1 <= k <= 1024
+        assert (mask is None) == (row_pred is None), \
+            "mask and row_pred go together"
+        if mask is not None:
+            # a producer histogram counts failing documents too
+            assert ext_hist1 is None, "ext_hist1 cannot be masked"
+            _check(mask, torch.int32, "mask")
+            _check(row_pred, torch.int32, "row_pred")
+            assert mask.dim() == 2 and mask.shape[1] * 32 >= N
+            assert row_pred.numel() == B
         if ext_hist1 is not None:
             # producer-fused pass 1 (bm25_block hist1=): exact counts
             assert ext_hist1.dtype == torch.int32 \
@@ -300,6 +314,12 @@ class TopK:
         self._ws[:lib.infomesh_topk_zero_u32(B)].zero_()
         vals = torch.empty((B, k), device=scores.device, dtype=torch.float32)
         idx = torch.empty((B, k), device=scores.device, dtype=torch.int32)
+        if mask is not None:
+            lib.infomesh_topk_masked(
+                scores.data_ptr(), self._ws.data_ptr(), vals.data_ptr(),
+                idx.data_ptr(), B, N, k, mask.data_ptr(),
+                row_pred.data_ptr(), mask.shape[1], _ext.stream_ptr())
+            return vals, idx
         lib.infomesh_topk(scores.data_ptr(), self._ws.data_ptr(),
                           vals.data_ptr(), idx.data_ptr(), B, N, k,
                           0 if ext_hist1 is None else ext_hist1.data_ptr(),
@@ -309,6 +329,25 @@ class TopK:
 
 def topk(scores: torch.Tensor, k: int) -> tuple[torch.Tensor, torch.Tensor]:
     return TopK(scores.device)(scores, k)
+
+
+def filter_bitmask(attrs: torch.Tensor, preds: torch.Tensor) -> torch.Tensor:
+    """Per-document attribute records [N, 4] i32 x predicates [P, 4] i32
+    (index/doc_attrs.py, layout in csrc/docfilter.hip) -> pass bitmask
+    [P, W] i32, W = ceil(N/64)*2; bit d&31 of word d>>5 is document d,
+    bits at positions >= N are 0."""
+    _check(attrs, torch.int32, "attrs")
+    _check(preds, torch.int32, "preds")
+    assert attrs.dim() == 2 and attrs.shape[1] == 4
+    assert preds.dim() == 2 and preds.shape[1] == 4 and preds.shape[0] >= 1
+    N, P = attrs.shape[0], preds.shape[0]
+    assert P <= 65535
+    W = (N + 63) // 64 * 2
+    bits = torch.empty((P, W), device=attrs.device, dtype=torch.int32)
+    _ext.lib().infomesh_filter_bitmask(
+        attrs.data_ptr(), preds.data_ptr(), bits.data_ptr(), N, P,
+        _ext.stream_ptr())
+    return bits
 
 
 def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,

@@ -150,6 +150,39 @@ def hamming_matches(queries: list[int], table: list[int],
     return out
 
 
+def filter_bitmask(attrs: torch.Tensor, preds: torch.Tensor) -> torch.Tensor:
+    """Oracle of csrc/docfilter.hip: attrs [N, 4] i32, preds [P, 4] i32
+    -> pass bits [P, W] i32, W = ceil(N/64)*2, zero at positions >= N."""
+    import numpy as np
+    from ..index.doc_attrs import passes
+    a = attrs.cpu().numpy()
+    N = a.shape[0]
+    W = (N + 63) // 64 * 2
+    rows = []
+    for pred in preds.cpu().numpy().view(np.uint32):
+        ok = np.zeros(W * 32, dtype=bool)
+        ok[:N] = passes(a, pred)
+        rows.append(np.packbits(ok, bitorder="little").view(np.uint32))
+    return torch.from_numpy(np.stack(rows).view(np.int32).reshape(-1, W))
+
+
+def masked_topk(scores: torch.Tensor, k: int, bits: torch.Tensor,
+                row_pred: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Oracle of the masked top-k: failing columns become -inf, then
+    torch.topk; -inf results carry index -1."""
+    import numpy as np
+    B, N = scores.shape
+    words = bits.cpu().numpy().view(np.uint32)
+    ok = np.unpackbits(words.view(np.uint8), axis=1,
+                       bitorder="little")[:, :N].astype(bool)
+    ok = torch.from_numpy(ok[row_pred.cpu().numpy().astype(np.int64)])
+    s = scores.detach().float().cpu().masked_fill(~ok, float("-inf"))
+    vals, idx = torch.topk(s, k, dim=1)
+    idx = torch.where(torch.isinf(vals) & (vals < 0),
+                      torch.full_like(idx, -1), idx)
+    return vals, idx
+
+
 def attn_decode(q: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, lens: torch.Tensor,
                 scale: float) -> torch.Tensor:

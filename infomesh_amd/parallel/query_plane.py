@@ -18,11 +18,18 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from ..index.doc_attrs import U32_MAX, pack_pred
 from ..index.gpu_index import GpuShard, ShardHits
 from .fabric import Fabric
 
 RRF_K = 60
 MAX_QUERY_TERMS = 32
+# Filter predicates ride in the terms broadcast as two extra int64
+# columns per row: x | y<<32 and z | w<<32 of doc_attrs.pack_pred. Bit 17
+# of z is unused by the predicate and marks "this row has a filter";
+# an unfiltered row carries two zeros.
+_PRED_COLS = 2
+_HAS_FILTER = 1 << 17
 
 
 @dataclass
@@ -124,8 +131,12 @@ class DistributedQueryPlane:
                      use_dense: bool = True,
                      phase_t: dict | None = None,
                      encode_fn=None,
-                     encode_shard=None) -> FusedHits | None:
-        """Collective search with rank-fault tolerance: on a collective
+                     encode_shard=None,
+                     filters: list | None = None) -> FusedHits | None:
+        """filters (rank 0): one DocFilter or None per row; every shard
+        applies them in its top-k selection.
+
+        Collective search with rank-fault tolerance: on a collective
         failure (dead rank → timeout) the fabric shrinks to the
         pre-created exclusion subgroup and the batch retries once,
         flagged degraded (reference parity: local-only serving when
@@ -133,7 +144,7 @@ class DistributedQueryPlane:
         try:
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
-                                      encode_fn, encode_shard)
+                                      encode_fn, encode_shard, filters)
         except RuntimeError as e:
             if not self.fabric.initialized or not self.fabric.collective_ok:
                 raise
@@ -166,7 +177,7 @@ class DistributedQueryPlane:
                     if r != self.fabric.rank))
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
-                                      encode_fn, encode_shard)
+                                      encode_fn, encode_shard, filters)
 
     def _sharded_encode(self, encode_shard: dict, B: int,
                         dim: int) -> torch.Tensor:
@@ -205,7 +216,7 @@ class DistributedQueryPlane:
                       B: int, dim: int = 384, n_results: int = 10,
                       use_dense: bool = True,
                       phase_t: dict | None = None,
-                      encode_fn=None, encode_shard=None
+                      encode_fn=None, encode_shard=None, filters=None
                       ) -> FusedHits | None:
         """One collective search attempt. Rank 0 passes real queries and
         gets the FusedHits; other ranks pass None and get None.
@@ -231,10 +242,12 @@ class DistributedQueryPlane:
             hits = self._search_overlapped(queries_terms, query_emb,
                                            encode_fn, B, dim, use_dense,
                                            phase_t=phase_t,
-                                           encode_shard=encode_shard)
+                                           encode_shard=encode_shard,
+                                           filters=filters)
             tp = mark("plane.shard", tp)
         else:
-            terms = self._broadcast_terms(queries_terms, B)
+            terms, filters = self._broadcast_terms(queries_terms, B,
+                                                   filters)
             if encode_shard is not None:
                 emb = self._sharded_encode(encode_shard, B, dim).float()
             else:
@@ -248,7 +261,8 @@ class DistributedQueryPlane:
             tp = mark("plane.pack", tp)
             hits = self.shard.search(
                 terms, emb if use_dense else None, k=self.k,
-                scores_buf=self._get_scores_buf(B), phase_t=phase_t)
+                scores_buf=self._get_scores_buf(B), phase_t=phase_t,
+                filters=filters)
             tp = mark("plane.shard", tp)
         # ONE packed all-gather instead of four: xGMI collectives at
         # this payload size (a few hundred KB) are latency-dominated,
@@ -305,7 +319,7 @@ class DistributedQueryPlane:
 
     def _search_overlapped(self, queries_terms, query_emb, encode_fn,
                            B, dim, use_dense, phase_t=None,
-                           encode_shard=None) -> ShardHits:
+                           encode_shard=None, filters=None) -> ShardHits:
         """BM25 on a side stream || query encoding on the main stream.
 
         Broadcast order (terms, then embeddings) is identical on all
@@ -328,13 +342,14 @@ class DistributedQueryPlane:
             self._bm25_stream = torch.cuda.Stream(dev)
         # terms must be broadcast before any rank's shard work
         tp = _time.perf_counter()
-        terms = self._broadcast_terms(queries_terms, B)
+        terms, filters = self._broadcast_terms(queries_terms, B, filters)
         tp = mark("ov.terms", tp)
         main = torch.cuda.current_stream(dev)
         self._bm25_stream.wait_stream(main)
         with torch.cuda.stream(self._bm25_stream):
             bm_vals, bm_idx = self.shard.search_bm25(
-                terms, self.k, scores_buf=self._get_scores_buf(B))
+                terms, self.k, scores_buf=self._get_scores_buf(B),
+                filters=filters)
             bm_ids = self.shard.to_global(bm_idx)
         tp = mark("ov.bm25", tp)
         if encode_shard is not None:
@@ -349,7 +364,8 @@ class DistributedQueryPlane:
             self.fabric.broadcast(emb_t)
         tp = mark("ov.encode", tp)
         if use_dense and self.shard.embeddings is not None:
-            dn_vals, dn_idx = self.shard.search_dense(emb_t, self.k)
+            dn_vals, dn_idx = self.shard.search_dense(emb_t, self.k,
+                                                      filters=filters)
             dn_ids = self.shard.to_global(dn_idx)
             tp = mark("ov.dense", tp)
         else:
@@ -360,21 +376,43 @@ class DistributedQueryPlane:
         return ShardHits(bm25_scores=bm_vals, bm25_ids=bm_ids,
                          dense_scores=dn_vals, dense_ids=dn_ids)
 
-    def _broadcast_terms(self, queries_terms, B):
+    def _broadcast_terms(self, queries_terms, B, filters=None):
+        """-> (terms, filters) as every rank must see them. At world > 1
+        the predicates ride in the one terms broadcast (packed words,
+        which the shards accept in place of DocFilter objects)."""
         if self.fabric.world == 1 and queries_terms is not None:
             # no collective needed: skip the pack + GPU round-trip +
             # device sync entirely
-            return queries_terms
+            return queries_terms, filters
         dev = self.fabric.device
-        terms_t = torch.full((B, MAX_QUERY_TERMS), -1, dtype=torch.int64)
+        T = MAX_QUERY_TERMS
+        terms_t = torch.full((B, T + _PRED_COLS), -1, dtype=torch.int64)
+        terms_t[:, T:] = 0
         if queries_terms is not None:
             for i, t in enumerate(queries_terms):
-                t = t[:MAX_QUERY_TERMS]
+                t = t[:T]
                 terms_t[i, :len(t)] = torch.from_numpy(t.astype(np.int64))
+            if filters is not None:
+                cols = np.zeros((B, _PRED_COLS), dtype=np.uint64)
+                for i, f in enumerate(filters):
+                    if f is None:
+                        continue
+                    x, y, z, w = pack_pred(f)
+                    cols[i] = (x | (y << 32), z | _HAS_FILTER | (w << 32))
+                terms_t[:, T:] = torch.from_numpy(cols.view(np.int64))
         terms_t = terms_t.to(dev)
         self.fabric.broadcast(terms_t)
         tt = terms_t.cpu().numpy()
-        return [tt[i][tt[i] >= 0] for i in range(B)]
+        cols = np.ascontiguousarray(tt[:, T:]).view(np.uint64)
+        has = (cols[:, 1] & np.uint64(_HAS_FILTER)) != 0
+        filters = None
+        if has.any():
+            filters = [
+                (int(c0) & U32_MAX, int(c0) >> 32,
+                 int(c1) & U32_MAX & ~_HAS_FILTER, int(c1) >> 32)
+                if h else None
+                for (c0, c1), h in zip(cols, has)]
+        return [tt[i, :T][tt[i, :T] >= 0] for i in range(B)], filters
 
     def _get_scores_buf(self, B: int) -> torch.Tensor | None:
         N = self.shard.n_docs

@@ -23,6 +23,7 @@ from .crawler.scheduler import Scheduler
 from .crawler.worker import CrawlResult, CrawlWorker
 from .engine import HybridEngine
 from .errors import GpuExtensionMissing, InfoMeshError
+from .index.doc_attrs import DocFilter
 from .index.link_graph import LinkGraph
 from .index.local_store import Document, LocalStore
 from .search.batcher import QueryBatcher
@@ -117,6 +118,10 @@ class AppContext:
             feeds=FeedMonitor(path=None if in_memory else p("feeds.json")),
             related=RelatedSearchTracker(),
         )
+        # GDPR / DMCA deletions reach the GPU engine at once (the
+        # engine may be attached later, so the hook looks it up)
+        ctx.deletions.on_delete = ctx._engine_forget
+        ctx.takedowns.on_delete = ctx._engine_forget
         from .search.feedback import FeedbackStore
         ctx.feedback = FeedbackStore(p("feedback.db"))
         from .utils.governor import ResourceGovernor
@@ -200,6 +205,15 @@ class AppContext:
         GLOBAL_PLUGINS.run("post_index", doc, rowid=rowid)
         return rowid
 
+    def _engine_forget(self, doc_ids: list[int]) -> int:
+        """Deletion hook of the GDPR / DMCA managers: tombstone the
+        rows on the GPU plane (no flush needed) and drop cached
+        responses that may still list them."""
+        self.cache.invalidate()
+        if self.engine is None:
+            return 0
+        return self.engine.delete_documents(doc_ids)
+
     def signed_attestations(self, limit: int = 100) -> list:
         """Serve the newest attestations, completing any deferred
         signatures (reference: attestations published to peers/DHT)."""
@@ -268,11 +282,14 @@ class AppContext:
         trust_fn = self.trust.trust_fn()
         engine_ready = (self.engine is not None
                         and self.engine.shard.n_docs > 0)
-        # Metadata filters (site:/language/date) live in the SQLite
-        # plane only — filtered queries take the FTS path even when the
-        # engine is up (reference local_store.py:253-352 filter SQL).
+        # Metadata filters (site:/language/date): by default filtered
+        # queries take the FTS path even when the engine is up
+        # (reference local_store.py:253-352 filter SQL); gpu.filters
+        # sends them to the engine's masked top-k instead.
         pq = parse_query_filters(query)
         has_filters = bool(pq.site or pq.after or pq.before or pq.language)
+        if self.config.gpu.filters:
+            has_filters = False
         if mode == "local" or (mode == "auto" and not engine_ready):
             resp = search_local(self.store, query, limit=limit,
                                 authority_fn=authority, trust_fn=trust_fn,
@@ -331,16 +348,33 @@ class AppContext:
         if self.batcher is not None \
                 and self.batcher.engine is not self.engine:
             self.batcher.engine = self.engine   # engine was rebound
-        per_q = self.engine.search_many(queries, limit=limit)
+        filters = None
+        sites: list[str | None] = [None] * len(queries)
+        if self.config.gpu.filters:
+            # filter tokens travel inside the query text (the batcher's
+            # signature knows nothing of them): split them off here,
+            # score the stripped text, filter inside the plane's top-k
+            parsed = [parse_query_filters(q) for q in queries]
+            filters = [
+                DocFilter(language=pq.language, site=pq.site,
+                          after=pq.after, before=pq.before)
+                if (pq.site or pq.language or pq.after or pq.before)
+                else None for pq in parsed]
+            queries = [pq.text for pq in parsed]
+            sites = [pq.site for pq in parsed]
+        per_q = self.engine.search_many(queries, limit=limit,
+                                        filters=filters)
         gids = [h.doc_id for hits in per_q for h in hits]
         docs = self.store.get_documents(gids)
         out: list[list] = []
-        for q, hits in zip(queries, per_q):
+        for q, hits, site in zip(queries, per_q, sites):
             hydrated = []
             for h in hits:
                 doc = docs.get(h.doc_id)
                 if doc is None:
                     continue
+                if site and doc.domain != site:
+                    continue   # 32-bit domain-hash collision guard
                 h.url, h.title = doc.url, doc.title
                 h.domain, h.crawled_at = doc.domain, doc.crawled_at
                 if doc.text:

@@ -54,10 +54,13 @@ class TakedownManager(SQLiteStore):
     """
 
     def __init__(self, store: LocalStore, kp: KeyPair | None = None,
-                 path: str | Path = ":memory:"):
+                 path: str | Path = ":memory:", on_delete=None):
         super().__init__(path)
         self.store = store
         self.kp = kp
+        # on_delete(doc_ids): told which rows a notice removed, so an
+        # index beside the store (the GPU engine) forgets them as well
+        self.on_delete = on_delete
 
     def file_notice(self, url_pattern: str, reason: str,
                     claimant: str) -> TakedownNotice:
@@ -90,10 +93,16 @@ class TakedownManager(SQLiteStore):
     def apply_pending(self) -> int:
         """Remove matching docs for unapplied notices; returns count."""
         removed_total = 0
+        gone: list[int] = []
         for row in self.execute(
                 "SELECT id, url_pattern FROM takedowns"
                 " WHERE applied_at IS NULL").fetchall():
             pattern = row["url_pattern"]
+            # ids first: after the delete the store cannot name them
+            if pattern.startswith("domain:"):
+                gone += self.store.doc_ids_where("domain", pattern[7:])
+            else:
+                gone += self.store.doc_ids_where("url", pattern)
             if pattern.startswith("domain:"):
                 removed = self.store.delete_by_domain(pattern[7:])
             else:
@@ -103,6 +112,8 @@ class TakedownManager(SQLiteStore):
                 " WHERE id=?", (time.time(), removed, row["id"]))
             removed_total += removed
         self.commit()
+        if gone and self.on_delete is not None:
+            self.on_delete(gone)
         return removed_total
 
     def overdue(self, now: float | None = None) -> list[dict]:

@@ -32,10 +32,13 @@ class DeletionManager(SQLiteStore):
     """
 
     def __init__(self, store: LocalStore, kp: KeyPair | None = None,
-                 path: str | Path = ":memory:"):
+                 path: str | Path = ":memory:", on_delete=None):
         super().__init__(path)
         self.store = store
         self.kp = kp
+        # on_delete(doc_ids): told which rows a record removed, so an
+        # index beside the store (the GPU engine) forgets them as well
+        self.on_delete = on_delete
 
     def request_deletion(self, subject: str, reason: str = "",
                          requester: str = "") -> dict:
@@ -61,8 +64,16 @@ class DeletionManager(SQLiteStore):
     def enforce(self) -> int:
         """Apply all deletion records against the store."""
         removed = 0
+        gone: list[int] = []
         for row in self.execute("SELECT id, subject FROM deletions").fetchall():
             s = row["subject"]
+            # ids first: after the delete the store cannot name them
+            if s.startswith("domain:"):
+                gone += self.store.doc_ids_where("domain", s[7:])
+            elif s.startswith("text_hash:"):
+                gone += self.store.doc_ids_where("text_hash", s[10:])
+            else:
+                gone += self.store.doc_ids_where("url", s)
             if s.startswith("domain:"):
                 n = self.store.delete_by_domain(s[7:])
             elif s.startswith("text_hash:"):
@@ -78,6 +89,8 @@ class DeletionManager(SQLiteStore):
                     " WHERE id=?", (n, row["id"]))
                 removed += n
         self.commit()
+        if gone and self.on_delete is not None:
+            self.on_delete(gone)
         return removed
 
     def is_forgotten(self, url: str) -> bool:
