@@ -279,13 +279,20 @@ class LocalStore:
                           crawled_at=r["crawled_at"]) for r in rows]
 
     def suggest(self, prefix: str, limit: int = 5) -> list[str]:
-        """Title-prefix suggestions (reference: local_store.py:354)."""
-        prefix = prefix.strip()
-        if not prefix:
+        """Title-prefix suggestions (reference: local_store.py:354).
+
+        The prefix is matched as given, ASCII case-insensitively:
+        callers that take typed input strip it first (the MCP suggest
+        handler does). A blank prefix suggests nothing."""
+        if not prefix.strip():
             return []
+        # the prefix is text, not a pattern: LIKE's wildcards in it
+        # ('%', '_') match themselves, and so does its white space
+        literal = (prefix.replace("\\", "\\\\").replace("%", "\\%")
+                   .replace("_", "\\_"))
         rows = self.conn.execute(
-            "SELECT title FROM documents WHERE title LIKE ? || '%'"
-            " ORDER BY crawled_at DESC LIMIT ?", (prefix, limit)).fetchall()
+            "SELECT title FROM documents WHERE title LIKE ? || '%' ESCAPE '\\'"
+            " ORDER BY crawled_at DESC LIMIT ?", (literal, limit)).fetchall()
         return [r["title"] for r in rows]
 
     # ------------------------------------------------------------- access

@@ -1,8 +1,9 @@
 // Per-row top-k selection over [B, N] f32 score arrays (N up to tens of
-// millions, K <= 1024) via 2-level radix select + compaction + one-block
-// bitonic sort. Replaces: ChromaDB HNSW top-k (reference
-// infomesh/index/vector_store.py:216-220) and the FTS5 ORDER BY bm25()
-// LIMIT path (index/local_store.py:316-332) on the GPU shards.
+// millions, K <= 1024) via radix select (2 byte levels, 4 on rows that
+// need them) + compaction + one-block bitonic sort. Replaces: ChromaDB
+// HNSW top-k (reference infomesh/index/vector_store.py:216-220) and the
+// FTS5 ORDER BY bm25() LIMIT path (index/local_store.py:316-332) on the
+// GPU shards.
 //
 // Passes, one launch each (3 streaming reads of the score array, 2 when
 // the producer supplies the pass-1 histogram):
@@ -10,16 +11,27 @@
 //      skipped when the caller passes ext_hist1.
 //   2. select1: find byte bin containing the Kth value.
 //   3. hist2: 256-bin histogram of byte 2 within that bin.
-//   4. select2: 16-bit threshold prefix.
+//   4. select2: 16-bit threshold prefix. A row where more candidates
+//      share that prefix than the tie region of the candidate buffer
+//      holds is refined in the same kernel, by its one workgroup: bytes
+//      3 and 4 of the threshold, two more reads of that row alone,
+//      giving a full 32-bit threshold.
 //   5. compact: gather (value, idx) — strictly-above candidates into a
-//      reserved region (provably < K of them), threshold-prefix-equal
-//      candidates until the cap (excess ties dropped: sound, they are
-//      interchangeable at rank K).
+//      reserved region (provably < K of them), threshold-equal
+//      candidates until the cap. On an unrefined row all of them fit;
+//      on a refined row they equal the threshold in all 32 bits, so the
+//      excess dropped at the cap is interchangeable at rank K.
 //   6. sort: one block per row bitonic-sorts candidates, emits top-K.
 //
-// Masked variant (infomesh_topk_masked): the three streaming kernels are
-// templated on MASKED and read a per-document pass bit (docfilter.hip's
-// [P, W] bitmask, row b using mask row row_pred[b]). A failing document
+// Exact for every row without NaN: the values returned are the K
+// largest, ordered by value, equal values by ascending index (+0.0 and
+// -0.0 count as equal there). Which of several EQUAL values at rank K
+// are returned is arbitrary.
+//
+// Masked variant (infomesh_topk_masked): the kernels that read scores
+// (hist1, hist2, select2's refinement, compact) are templated on MASKED
+// and read a per-document pass bit (docfilter.hip's [P, W] bitmask,
+// row b using mask row row_pred[b]). A failing document
 // is absent: not histogrammed, not compacted; rows with fewer than K
 // passing documents pad with -inf / -1. One u32 of mask covers one
 // 128-byte line of scores, and the mask word is loaded first (one loop
@@ -28,6 +40,26 @@
 #include "common.h"
 
 #define TOPK_CAP 8192
+
+// Candidate layout per row (TOPK_CAP slots):
+//   [0, HI_RES)        strictly-above-threshold candidates. Fewer than
+//                      K <= 1024 exist (see compact_kernel), so the
+//                      reserve is generous; its size also fixes where
+//                      the tie region starts, i.e. how many ties
+//                      survive and how large the sort gets on tied rows.
+//   [HI_RES, TOPK_CAP) threshold-equal candidates, kept until the
+//                      region fills. Where more candidates share the
+//                      16-bit threshold prefix than fit here, the
+//                      row's threshold is refined to all 32 bits
+//                      (select2_kernel), and only candidates EQUAL to it
+//                      land here. Those are interchangeable at rank K
+//                      (any K of them is a valid top-k), so DROPPING
+//                      the excess is sound: massively tied planes (BM25
+//                      over tiny-vocab corpora) do not overflow.
+//                      Candidates that share a prefix and differ below
+//                      it are never dropped; the final bitonic sorts
+//                      them by the full 32-bit ordered value.
+#define HI_RES 4096
 
 namespace {
 
@@ -150,33 +182,11 @@ __global__ void select1_kernel(const unsigned* __restrict__ hist,
   chi1[b] = cum;
 }
 
-__global__ void select2_kernel(const unsigned* __restrict__ hist2,
-                               const unsigned* __restrict__ bin1,
-                               const unsigned* __restrict__ chi1,
-                               unsigned* __restrict__ thresh16, int K) {
-  const int b = blockIdx.x;
-  if (threadIdx.x != 0) return;
-  unsigned cum = chi1[b];
-  thresh16[b] = (bin1[b] << 8) | select_bin(hist2 + (long)b * 256, cum, K);
-}
-
-template <bool MASKED, typename... M>
-__global__ __launch_bounds__(256) void hist2_kernel(
-    const float* __restrict__ scores, const unsigned* __restrict__ bin1,
-    unsigned* __restrict__ hist2, long N, M... mask) {
-  __shared__ unsigned lh[256];
-  const int b = blockIdx.y;
-  const unsigned b1 = bin1[b];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) lh[i] = 0;
-  __syncthreads();
-  const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long step = (long)gridDim.x * blockDim.x;
-  const float* row = scores + (long)b * N;
-  const long n4 = N / 4;
-  auto count = [&](float f) {
-    const unsigned o = float_to_ordered(f);
-    if ((o >> 24) == b1) atomicAdd(&lh[(o >> 16) & 255], 1u);
-  };
+// count(value) for every (passing) column of batch row b, the columns
+// dealt to threads from `start` in steps of `step`.
+template <bool MASKED, typename F, typename... M>
+DEVINL void for_each_score(const float* __restrict__ row, long N, int b,
+                           long start, long step, F count, M... mask) {
   if constexpr (MASKED) {
     masked_stream(
         row, mask_row(mask..., b), N, start, step,
@@ -188,47 +198,114 @@ __global__ __launch_bounds__(256) void hist2_kernel(
         },
         [&](float f, long) { count(f); });
   } else {
+    const long n4 = N / 4;
     for (long i = start; i < n4; i += step) {
       const float4 v = reinterpret_cast<const float4*>(row)[i];
       count(v.x); count(v.y); count(v.z); count(v.w);
     }
     for (long i = n4 * 4 + start; i < N; i += step) count(row[i]);
   }
+}
+
+template <bool MASKED, typename... M>
+__global__ __launch_bounds__(256) void hist2_kernel(
+    const float* __restrict__ scores, const unsigned* __restrict__ bin1,
+    unsigned* __restrict__ hist2, long N, M... mask) {
+  __shared__ unsigned lh[256];
+  const int b = blockIdx.y;
+  const unsigned b1 = bin1[b];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) lh[i] = 0;
+  __syncthreads();
+  for_each_score<MASKED>(
+      scores + (long)b * N, N, b,
+      (long)blockIdx.x * blockDim.x + threadIdx.x,
+      (long)gridDim.x * blockDim.x,
+      [&](float f) {
+        const unsigned o = float_to_ordered(f);
+        if ((o >> 24) == b1) atomicAdd(&lh[(o >> 16) & 255], 1u);
+      },
+      mask...);
   __syncthreads();
   for (int i = threadIdx.x; i < 256; i += blockDim.x)
     if (lh[i]) atomicAdd(&hist2[(long)b * 256 + i], lh[i]);
 }
 
-// Candidate layout per row (TOPK_CAP slots):
-//   [0, HI_RES)        strictly-above-threshold candidates. Fewer than
-//                      K <= 1024 exist (see compact_kernel), so the
-//                      reserve is generous; its size also fixes where
-//                      the tie region starts, i.e. how many ties
-//                      survive and how large the sort gets on tied rows.
-//   [HI_RES, TOPK_CAP) threshold-PREFIX-EQUAL candidates, kept until
-//                      the region fills. Prefix-equal candidates are
-//                      interchangeable at rank K (any K of them is a
-//                      valid top-k), so DROPPING the excess is sound:
-//                      massively tied planes (BM25 over tiny-vocab
-//                      corpora) do not overflow. The final bitonic
-//                      sorts by the full 32-bit ordered value, so
-//                      prefix-equal candidates still order exactly.
-#define HI_RES 4096
+// One workgroup per row. Thread 0 finds the 16-bit threshold prefix.
+// If every candidate sharing that prefix fits the tie region of the
+// candidate buffer (all but degenerate rows), that is the row's
+// threshold, shift[b] = 16 tells compact_kernel to compare the top 16
+// bits, and the workgroup is done.
+// Otherwise compact_kernel would have to drop candidates that differ
+// below the prefix, so the workgroup refines the threshold to all 32
+// bits here (shift[b] = 0): for bytes 3 and 4 in turn it streams the
+// row, histograms that byte among the values matching the prefix so
+// far, and extends the prefix by the bin holding the Kth value. Two
+// more reads of the row by ONE workgroup: slow next to the grid-wide
+// passes (a single CU's bandwidth), but it costs the rows that need no
+// refinement nothing, not even a launch.
+#define SELECT2_THREADS 1024
+template <bool MASKED, typename... M>
+__global__ __launch_bounds__(SELECT2_THREADS) void select2_kernel(
+    const float* __restrict__ scores, const unsigned* __restrict__ hist2,
+    const unsigned* __restrict__ bin1, const unsigned* __restrict__ chi1,
+    unsigned* __restrict__ thresh, unsigned* __restrict__ shift, long N,
+    int K, M... mask) {
+  __shared__ unsigned lh[256];
+  __shared__ unsigned s_pre, s_cum, s_refine;
+  const int b = blockIdx.x;
+  if (threadIdx.x == 0) {
+    const unsigned* h = hist2 + (long)b * 256;
+    unsigned cum = chi1[b];
+    const unsigned bin = select_bin(h, cum, K);
+    s_pre = (bin1[b] << 8) | bin;
+    s_cum = cum;
+    s_refine = h[bin] > TOPK_CAP - HI_RES;
+  }
+  __syncthreads();
+  if (!s_refine) {
+    if (threadIdx.x == 0) { thresh[b] = s_pre; shift[b] = 16; }
+    return;
+  }
+  for (int sh = 8; sh >= 0; sh -= 8) {
+    const unsigned pre = s_pre;
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) lh[i] = 0;
+    __syncthreads();
+    for_each_score<MASKED>(
+        scores + (long)b * N, N, b, (long)threadIdx.x, (long)blockDim.x,
+        [&](float f) {
+          const unsigned o = float_to_ordered(f);
+          if ((o >> sh >> 8) == pre) atomicAdd(&lh[(o >> sh) & 255], 1u);
+        },
+        mask...);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned cum = s_cum;
+      s_pre = (pre << 8) | select_bin(lh, cum, K);
+      s_cum = cum;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { thresh[b] = s_pre; shift[b] = 0; }
+}
 
-// The `pos < HI_RES` guard never trips here: select1/select2 pick the
-// highest bin at which the cumulative count reaches K, so the count
-// strictly above the 16-bit threshold is below K <= 1024 < HI_RES, and
-// the bin-0 fall-through (N < K) counts fewer still. Both guards stay as
-// the memory-safety bound, also against a wrong producer histogram.
+// The `pos < HI_RES` guard never trips here: every select level picks
+// the highest bin at which the cumulative count reaches K, so the count
+// strictly above the threshold is below K <= 1024 < HI_RES, and the
+// bin-0 fall-through (N < K) counts fewer still. The tie-region guard
+// trips only on a refined row, whose threshold has all 32 bits. Both
+// guards stay as the memory-safety bound, also against a wrong producer
+// histogram.
 // MASKED: the argument holds as is, over the passing documents alone —
 // the histograms counted exactly the documents this kernel emits.
 template <bool MASKED, typename... M>
 __global__ __launch_bounds__(256) void compact_kernel(
-    const float* __restrict__ scores, const unsigned* __restrict__ thresh16,
+    const float* __restrict__ scores, const unsigned* __restrict__ thresh,
+    const unsigned* __restrict__ shift,
     unsigned long long* __restrict__ cand, unsigned* __restrict__ cnt,
     unsigned* __restrict__ cnt_eq, long N, M... mask) {
   const int b = blockIdx.y;
-  const unsigned t16 = thresh16[b];
+  // the row's threshold: the top 16 bits (sh = 16), or all 32 (sh = 0)
+  const unsigned t = thresh[b], sh = shift[b];
   const long start = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long step = (long)gridDim.x * blockDim.x;
   const float* row = scores + (long)b * N;
@@ -236,14 +313,14 @@ __global__ __launch_bounds__(256) void compact_kernel(
   const long n4 = N / 4;
   auto emit = [&](float f, unsigned idx) {
     const unsigned o = float_to_ordered(f);
-    const unsigned p16 = o >> 16;
+    const unsigned p = o >> sh;
     // Ascending sort key: ~ordered in high bits (desc value),
     // raw idx in low bits (ties -> smaller idx first).
     const unsigned long long key = ((unsigned long long)(~o) << 32) | idx;
-    if (p16 > t16) {
+    if (p > t) {
       const unsigned pos = atomicAdd(&cnt[b], 1u);
       if (pos < HI_RES) crow[pos] = key;
-    } else if (p16 == t16) {
+    } else if (p == t) {
       const unsigned pos = atomicAdd(&cnt_eq[b], 1u);
       if (pos < TOPK_CAP - HI_RES) crow[HI_RES + pos] = key;
     }
@@ -284,10 +361,19 @@ __global__ __launch_bounds__(256) void sort_emit_kernel(
   int n2 = 64;
   while (n2 < n) n2 <<= 1;
   const unsigned long long* crow = cand + (long)b * TOPK_CAP;
-  for (int i = threadIdx.x; i < n2; i += blockDim.x)
-    d[i] = (i < nhi) ? crow[i]
-         : (i < n) ? crow[HI_RES + (i - nhi)]
-         : ~0ULL;  // pad = worst
+  for (int i = threadIdx.x; i < n2; i += blockDim.x) {
+    unsigned long long key = (i < nhi) ? crow[i]
+                           : (i < n) ? crow[HI_RES + (i - nhi)]
+                           : ~0ULL;  // pad = worst
+    // -0.0 (high key word 0x80000000) takes +0.0's (0x7fffffff): the
+    // two compare equal, so they order by index among themselves, and
+    // the value emitted for either is +0.0. On purpose only here:
+    // select and compact still rank -0.0 strictly below +0.0, which
+    // only decides WHICH of the equal zeros are returned at rank K, and
+    // that is arbitrary anyway.
+    if ((unsigned)(key >> 32) == 0x80000000u) key -= 1ULL << 32;
+    d[i] = key;
+  }
   __syncthreads();
   for (int k = 2; k <= n2; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -316,13 +402,13 @@ __global__ __launch_bounds__(256) void sort_emit_kernel(
 
 // Workspace layout, offsets in u32 units. The caller zeroes [0, cand)
 // before every call (hist1, hist2, cnt and cnt_eq accumulate by atomics;
-// the three select outputs ride along in the same fill).
+// the four select outputs ride along in the same fill).
 struct TopkLayout {
-  long hist1, hist2, bin1, chi1, thresh16, cnt, cnt_eq, cand, total;
+  long hist1, hist2, bin1, chi1, thresh, shift, cnt, cnt_eq, cand, total;
   explicit TopkLayout(long B)
       : hist1(0), hist2(hist1 + B * 256), bin1(hist2 + B * 256),
-        chi1(bin1 + B), thresh16(chi1 + B), cnt(thresh16 + B),
-        cnt_eq(cnt + B),
+        chi1(bin1 + B), thresh(chi1 + B), shift(thresh + B),
+        cnt(shift + B), cnt_eq(cnt + B),
         cand((cnt_eq + B + 1) & ~1L),  // u64 candidates: 8-byte aligned
         total(cand + B * TOPK_CAP * 2) {}
 };
@@ -361,11 +447,12 @@ static void topk_launch(const void* scores, void* workspace, void* out_vals,
   hipLaunchKernelGGL((hist2_kernel<MASKED, M...>), g1, blk, 0, s,
                      (const float*)scores, ws + L.bin1, ws + L.hist2, N,
                      mask...);
-  hipLaunchKernelGGL(select2_kernel, dim3(B), dim3(64), 0, s,
-                     ws + L.hist2, ws + L.bin1, ws + L.chi1,
-                     ws + L.thresh16, K);
+  hipLaunchKernelGGL((select2_kernel<MASKED, M...>), dim3(B),
+                     dim3(SELECT2_THREADS), 0, s, (const float*)scores,
+                     ws + L.hist2, ws + L.bin1, ws + L.chi1, ws + L.thresh,
+                     ws + L.shift, N, K, mask...);
   hipLaunchKernelGGL((compact_kernel<MASKED, M...>), g1, blk, 0, s,
-                     (const float*)scores, ws + L.thresh16, cand,
+                     (const float*)scores, ws + L.thresh, ws + L.shift, cand,
                      ws + L.cnt, ws + L.cnt_eq, N, mask...);
   hipLaunchKernelGGL(sort_emit_kernel, dim3(B), blk, 0, s,
                      cand, ws + L.cnt, ws + L.cnt_eq, (float*)out_vals,

@@ -90,6 +90,28 @@ def test_suggest(seeded_store):
     assert any("Python" in s for s in seeded_store.suggest("Python"))
 
 
+def test_suggest_prefix_is_literal(store):
+    """LIKE's wildcards, the escape character and white space in the
+    prefix match themselves and nothing else."""
+    titles = ["_under", "0zero", "%pct", "100% sure", "back\\slash",
+              "backXslash", " lead", "lead", "Py thon", "Python"]
+    for i, t in enumerate(titles):
+        store.add_document(Document(url=f"http://s/{i}", title=t,
+                                    text=f"body {i} unique{i}"))
+    assert store.suggest("_", limit=20) == ["_under"]
+    assert store.suggest("%", limit=20) == ["%pct"]
+    assert store.suggest("100%", limit=20) == ["100% sure"]
+    assert store.suggest("back\\", limit=20) == ["back\\slash"]
+    assert store.suggest("back_", limit=20) == []
+    assert store.suggest(" l", limit=20) == [" lead"]
+    assert sorted(store.suggest("l", limit=20)) == ["lead"]
+    assert store.suggest("Py ", limit=20) == ["Py thon"]
+    assert sorted(store.suggest("py", limit=20)) == ["Py thon", "Python"]
+    assert store.suggest("   ") == [] and store.suggest("") == []
+    assert len(store.suggest("", limit=3)) == 0
+    assert len(store.suggest("p", limit=1)) == 1
+
+
 def test_delete(seeded_store):
     n = seeded_store.count()
     assert seeded_store.delete_by_url("https://pytorch.org/docs/")
