@@ -134,6 +134,8 @@ class GpuShard:
         self._live_bits = None   # cached live-only mask (+ ready event)
         self._topk = None
         self._topk_dense = None
+        self._topk_pruned = None    # dense selector over block maxima
+        self._dense_bmax: dict = {}  # [B, NB] block maxima, per B
         self._dense_graphs: dict = {}
         # hipGraph-capture the dense plane; set by the overlapped query
         # plane, off for direct search() callers
@@ -455,6 +457,7 @@ class GpuShard:
         # dense hipGraphs captured the old embeddings view/shape
         self._dense_graphs = {}
         self._dense_bufs = {}
+        self._dense_bmax = {}
         self._bm25_hists = {}
         self._live_bits = None
 
@@ -866,8 +869,11 @@ class GpuShard:
                 # A selector of its own per graph: replays keep writing
                 # the workspace recorded at capture, which a selector
                 # shared across batch sizes would free when it regrows.
-                def _plane(e, _B=B, _k=k, _emb=emb, _tk=K.TopK(self.device)):
-                    return _tk(self._dense_gemm(e, _emb, _B, self.n_docs), _k)
+                def _plane(e, _B=B, _k=k, _emb=emb,
+                           _tk=(K.TopK(self.device),
+                                K.TopKPruned(self.device))):
+                    return self._dense_select(
+                        self._dense_gemm(e, _emb, _B, self.n_docs), _k, *_tk)
                 g = self._dense_graphs[(B, k)] = GraphedCallable(_plane)
             vals, idx = g(query_emb.bfloat16())
             # detach from the graph's static outputs (next replay
@@ -875,21 +881,37 @@ class GpuShard:
             out = (vals.clone(), idx.clone())
             mark("shard.dense+topk", tp)
             return out
-        d_scores = self._dense_gemm(query_emb, emb, B, N)
+        d_scores = self._dense_gemm(query_emb, emb, B, N,
+                                    with_bmax=mask is None)
         tp = mark("shard.dense", tp)
         if mask is None:
-            out = self._get_topk_dense()(d_scores, k)
+            if self._topk_pruned is None:
+                self._topk_pruned = K.TopKPruned(self.device)
+            out = self._dense_select(d_scores, k, self._get_topk_dense(),
+                                     self._topk_pruned)
         else:
             out = self._get_topk_dense()(d_scores, k, mask=mask[0],
                                          row_pred=mask[1])
         mark("shard.densetopk", tp)
         return out
 
+    @staticmethod
+    def _dense_select(d_scores, k: int, topk, topk_pruned):
+        """Top-k of what _dense_gemm returned: from the block maxima
+        when it wrote them, else the streaming selector."""
+        if isinstance(d_scores, tuple):
+            return topk_pruned(*d_scores, k)
+        return topk(d_scores, k)
+
     def _dense_gemm(self, query_emb: torch.Tensor, emb: torch.Tensor,
-                    B: int, N: int) -> torch.Tensor:
+                    B: int, N: int, with_bmax: bool = True):
         """Dense cosine scores [B, N] on the stored-embedding dtype:
         bf16 -> generic MFMA tile; fp8 -> streaming fp8 kernel (M
-        chunks of <=128; query quantized per batch)."""
+        chunks of <=128; query quantized per batch).
+        with_bmax (unmasked batches; a mask would have to keep failing
+        documents out of the maxima): on the bf16 plane, where the GEMM
+        has the variant for this shape, returns (scores, bmax, W) with
+        the block maxima for the pruned selector."""
         from ..ops import kernels as K
         buf = self._get_dense_buf(B)
         if self.emb_dtype == "fp8":
@@ -903,6 +925,17 @@ class GpuShard:
                                        out=out2d[m0:m1])
                 assert r is not None, "fp8 dense plane shape ineligible"
             return out2d
+        W = K.gemm_bmax_width(B, N, emb.shape[1]) if with_bmax else 0
+        if W:
+            bmax = self._dense_bmax.get(B)
+            if bmax is None or bmax.shape != (B, (N + W - 1) // W):
+                # per B and dropped with the score buffers, for the
+                # reason given in _get_dense_buf
+                bmax = self._dense_bmax[B] = torch.empty(
+                    B, (N + W - 1) // W, device=self.device,
+                    dtype=torch.float32)
+            return K.gemm_nt_bmax(query_emb.bfloat16().contiguous(), emb,
+                                  out=buf.reshape(B, N), bmax=bmax)
         return K.gemm_nt(query_emb.bfloat16().unsqueeze(0), emb,
                          out_f32=True, out=buf).reshape(B, N)
 

@@ -95,12 +95,26 @@ _SIGNATURES: dict[str, list] = {
     "infomesh_silu_mul_fused": [c_void_p, c_void_p, c_long, c_int,
                                 c_void_p],
     "infomesh_gemm_tile": [c_int, c_int, c_int, c_int],
+    "infomesh_gemm_bmax_width": [c_int, c_int, c_int, c_int],
+    "infomesh_gemm_bf16_nt_bmax": [c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_int, c_int, c_int,
+                                   c_long, c_long, c_long,
+                                   c_int, c_float, c_void_p],
+    "infomesh_topk_pruned": [c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                             c_void_p, c_int, c_long, c_int, c_void_p],
+    "infomesh_topk_pruned_workspace_u32": [c_int, c_long, c_int, c_int],
+    "infomesh_topk_pruned_zero_u32": [c_int],
 }
 
 # Everything not listed here returns void. topk_*_u32: lengths;
-# dense_scores: dispatch eligibility (0 = launched); gemm_tile: tile code.
+# dense_scores, gemm_bf16_nt_bmax: dispatch eligibility (0 = launched);
+# gemm_tile: tile code; gemm_bmax_width: columns per block maximum.
 _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
              "infomesh_topk_zero_u32": c_long,
+             "infomesh_topk_pruned_workspace_u32": c_long,
+             "infomesh_topk_pruned_zero_u32": c_long,
+             "infomesh_gemm_bmax_width": c_int,
+             "infomesh_gemm_bf16_nt_bmax": c_int,
              "infomesh_dense_scores": c_int,
              "infomesh_dense_scores_fp8": c_int,
              "infomesh_gemm_tile": c_int}

@@ -15,6 +15,11 @@
 
 namespace {
 
+// Blocks of W columns in a row of N.
+__host__ DEVINL long bmax_blocks(int N, int W) { return ((long)N + W - 1) / W; }
+// The one pointer of a BMAX kernel's parameter pack.
+DEVINL float* bmax_of(float* p) { return p; }
+
 // Tile configurations (4 waves each):
 //   (128,128): 2x2 wave grid, 64x64 per wave (4x4 fragments) — default.
 //   ( 64,128): 1x4 grid, 64x32 per wave — skinny-M (query scoring).
@@ -25,13 +30,23 @@ namespace {
 //              gemm_pipe64_kernel below.
 // The BK=64 images are swizzled (swz); BK=32 rows are 64 B and keep
 // the linear image.
-template <int BM, int BN, int BK, bool OUT_F32>
+// BMAX (f32 output only): the kernel also writes each row's maximum over
+// every wave's column span W = BN / WN to bmax [batch, M, ceil(N / W)]:
+// bmax[g][m][j] = max of C[g][m][j*W .. j*W+W-1] over the columns < N
+// (gemm_common.h epilogues). The pointer is a parameter pack that is
+// empty when !BMAX, so the plain instantiations keep the signature,
+// the kernarg layout and hence the code they had without it (the
+// MaskRef pack of topk.hip does the same).
+template <int BM, int BN, int BK, bool OUT_F32, bool BMAX = false,
+          typename... BmaxPtr>
 __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     void* __restrict__ C, const float* __restrict__ bias,
     int M, int N, int K,
     long strideA, long strideB, long strideC,
-    int act, float alpha) {
+    int act, float alpha, BmaxPtr... bmax) {
+  static_assert(sizeof...(BmaxPtr) == (BMAX ? 1 : 0) && (OUT_F32 || !BMAX),
+                "one float* iff BMAX, and BMAX is f32 only");
   // One __shared__ object only (glds pipeline rule, guide §5 item 4a).
   // Layout per buffer: A tile [BM*BK] then B tile [BN*BK].
   __shared__ bf16 smem[2][(BM + BN) * BK];
@@ -142,19 +157,38 @@ __global__ __launch_bounds__(256) void gemm_bf16_nt_kernel(
   // through the LDS-staged nontemporal path; partial tiles and bf16
   // outputs keep the direct scalar path.
   const int m_base = m0 + wm * (BM / WM), n_base = n0 + wn * (BN / WN);
-  if (OUT_F32 && n0 + BN <= N && m0 + BM <= M) {
+  // The f32 tile has to fit the operand buffers it is staged in: with
+  // BK = 32 the 128-column tiles' do not (32 KB of smem for a 64 KB
+  // tile), and staging them anyway lost the rows past the end of smem
+  // (LDS writes out of range are dropped, the readback gave zeros).
+  constexpr bool STAGE_FITS = BM * BN * 4 <= (int)sizeof(smem);
+  if (OUT_F32 && STAGE_FITS && n0 + BN <= N && m0 + BM <= M) {
     // reuse the (drained) double buffer as an f32 staging tile:
     // per wave a [BM/WM][BN/WN] block = 64x64 (or 64x32/32x32) f32
     float* stage_f32 = reinterpret_cast<float*>(&smem[0][0])
         + wid * (BM / WM) * (BN / WN);
     __syncthreads();   // all MFMA reads of smem are done
-    store_frags_staged_f32(acc, stage_f32, reinterpret_cast<float*>(C),
-                           (long)g * strideC, bias, m_base, n_base, N,
-                           act, alpha, lane);
+    if constexpr (BMAX)
+      store_frags_staged_f32<FM, FN, true>(
+          acc, stage_f32, reinterpret_cast<float*>(C), (long)g * strideC,
+          bias, m_base, n_base, N, act, alpha, lane,
+          bmax_of(bmax...) + (long)g * M * bmax_blocks(N, BN / WN),
+          bmax_blocks(N, BN / WN));
+    else
+      store_frags_staged_f32(acc, stage_f32, reinterpret_cast<float*>(C),
+                             (long)g * strideC, bias, m_base, n_base, N,
+                             act, alpha, lane);
     return;
   }
-  store_frags_guarded<OUT_F32>(acc, C, (long)g * strideC, bias,
-                               m_base, n_base, M, N, N, act, alpha, lane);
+  if constexpr (BMAX)
+    store_frags_guarded_bmax(
+        acc, reinterpret_cast<float*>(C), (long)g * strideC, bias, m_base,
+        n_base, M, N, act, alpha, lane,
+        bmax_of(bmax...) + (long)g * M * bmax_blocks(N, BN / WN),
+        bmax_blocks(N, BN / WN));
+  else
+    store_frags_guarded<OUT_F32>(acc, C, (long)g * strideC, bias,
+                                 m_base, n_base, M, N, N, act, alpha, lane);
 }
 
 // ---- 3-buffer glds-span pipelined 64x64 tile ---------------------------
@@ -340,6 +374,32 @@ int tile_override() {
   return ov;
 }
 
+// The bmax variant always runs a generic tile with 128 columns, 64x128
+// at M <= 64 and 128x128 above: pick_tile without its step down to the
+// 64x64 tiles, which would need maxima instantiations of their own (and
+// of the pipelined kernel) to serve planes of a few thousand documents,
+// where the GEMM is microseconds either way. Every tile adds a score's
+// K-steps in the same order, so the scores do not depend on the choice.
+// bm == 0: not covered (the override forces 64x64).
+GemmTile bmax_tile(int M, int K, int force) {
+  if (force == 64 && M > 64) return {0, 0, 0, false};
+  return {(M <= 64 && force != 128) ? 64 : 128, 128,
+          (K % 64 == 0) ? 64 : 32, false};
+}
+// Columns per block maximum: the wave's column span BN / WN.
+int bmax_width(GemmTile t) { return t.bm == 0 ? 0 : t.bm == 128 ? 64 : 32; }
+
+template <int BM, int BK>
+void launch_bmax(dim3 grid, hipStream_t s, const void* A, const void* B,
+                 void* C, const void* bias, void* bmax, int M, int N, int K,
+                 long strideA, long strideB, long strideC, int act,
+                 float alpha) {
+  hipLaunchKernelGGL((gemm_bf16_nt_kernel<BM, 128, BK, true, true, float*>),
+                     grid, dim3(256), 0, s, (const bf16*)A, (const bf16*)B,
+                     C, (const float*)bias, M, N, K, strideA, strideB,
+                     strideC, act, alpha, (float*)bmax);
+}
+
 }  // namespace
 
 // The tile infomesh_gemm_bf16_nt runs this shape on, packed as
@@ -363,4 +423,29 @@ extern "C" void infomesh_gemm_bf16_nt(
                      M, N, K, strideA, strideB, strideC, act, alpha);
 }
 
+// Column span W of one block maximum of infomesh_gemm_bf16_nt_bmax at
+// this shape (64 on the 128x128 tile, 32 on the 64x128 one), or 0 when
+// the variant does not cover it. Callers size bmax by it:
+// [batch, M, ceil(N / W)] f32.
+extern "C" int infomesh_gemm_bmax_width(int M, int N, int K, int batch) {
+  return bmax_width(bmax_tile(M, K, tile_override()));
+}
 
+// infomesh_gemm_bf16_nt with f32 output, plus the block maxima of every
+// row (the BMAX instantiations, tile by bmax_tile). Same scores bit for
+// bit. Returns 0, or 1 without launching when the width above is 0.
+extern "C" int infomesh_gemm_bf16_nt_bmax(
+    const void* A, const void* B, void* C, const void* bias, void* bmax,
+    int M, int N, int K, int batch,
+    long strideA, long strideB, long strideC,
+    int act, float alpha, void* stream) {
+  const GemmTile t = bmax_tile(M, K, tile_override());
+  if (bmax_width(t) == 0) return 1;
+  const dim3 grid(((M + t.bm - 1) / t.bm) * ((N + t.bn - 1) / t.bn), batch);
+  auto* launch = t.bm == 128
+      ? (t.bk == 64 ? launch_bmax<128, 64> : launch_bmax<128, 32>)
+      : (t.bk == 64 ? launch_bmax<64, 64> : launch_bmax<64, 32>);
+  launch(grid, reinterpret_cast<hipStream_t>(stream), A, B, C, bias, bmax,
+         M, N, K, strideA, strideB, strideC, act, alpha);
+  return 0;
+}

@@ -79,18 +79,49 @@ DEVINL void store_frags_guarded(const f32x4 (&acc)[FM][FN], void* C,
   }
 }
 
+template <int CTRL>
+DEVINL uint32_t max_dpp(uint32_t v) {   // max(v, v of the lane CTRL names)
+  return max(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL,
+                                                      0xf, 0xf, false));
+}
+// Maximum of o over each aligned group of G (8 or 16) lanes, returned in
+// every lane of the group. DPP moves inside a 16-lane row — both quad
+// swaps, then the half-row and (G = 16) row mirrors — so it costs four
+// VALU ops and no LDS traffic, where __shfl_xor is a ds_bpermute each.
+// Every lane of the wave must be active.
+template <int G>
+DEVINL uint32_t group_max_u32(uint32_t o) {
+  static_assert(G == 8 || G == 16, "a half or a whole DPP row");
+  o = max_dpp<0xB1>(o);                 // quad_perm [1,0,3,2]
+  o = max_dpp<0x4E>(o);                 // quad_perm [2,3,0,1]
+  o = max_dpp<0x141>(o);                // row_half_mirror
+  if (G == 16) o = max_dpp<0x140>(o);   // row_mirror
+  return o;
+}
+
 // f32 output of a FULL tile: stage the wave's [FM*16][FN*16] block
 // through LDS (stage_f32, the wave's own region of the drained
 // operand buffers) and emit 16-B dwordx4 stores, NONTEMPORAL — C is
 // written once and next read by the streaming top-k, so allocating it
 // in L2 only evicts the B rows being streamed. The caller has made
 // sure nobody still reads or glds-writes the operand buffers.
-template <int FM, int FN>
+// BMAX: also write the maximum of each row of the wave block (W = SEGN
+// consecutive columns, block n_base / SEGN of the row) to
+// bmax[m * NB + block], taken from the f32x4 each lane reads back —
+// the values stored, so the maximum is of the scores bit for bit. The
+// order is the top-k selector's (float_to_ordered: -0.0 < +0.0).
+// The LPR lanes that read a row back reduce it among themselves, lane c
+// of the group keeps the result of iteration c, and after the LPR
+// iterations the wave's 64 lanes hold its 64 row maxima: one 4-byte
+// store each. These are NOT nontemporal: the neighbouring n-tiles fill
+// the rest of the line, which merges in L2.
+template <int FM, int FN, bool BMAX = false>
 DEVINL void store_frags_staged_f32(const f32x4 (&acc)[FM][FN],
                                    float* stage_f32, float* C, long c_off,
                                    const float* bias, int m_base,
                                    int n_base, int N, int act,
-                                   float alpha, int lane) {
+                                   float alpha, int lane,
+                                   float* bmax = nullptr, long NB = 0) {
   constexpr int SEGN = FN * 16;                  // cols of the wave block
   const int crow_base = (lane >> 4) * 4;
   const int ccol = lane & 15;
@@ -111,7 +142,10 @@ DEVINL void store_frags_staged_f32(const f32x4 (&acc)[FM][FN],
   // each lane streams 16 B of a row segment
   constexpr int LPR = SEGN * 4 / 16;             // lanes per row
   constexpr int ROWS_PER_IT = 64 / LPR;
+  static_assert(!BMAX || FM * 16 == LPR * ROWS_PER_IT,
+                "BMAX: 64 rows per wave, one maximum per lane");
   const int srow = lane / LPR, scol4 = (lane % LPR) * 4;
+  uint32_t mine = 0;       // ordered key of this lane's row maximum
 #pragma unroll
   for (int base = 0; base < FM * 16; base += ROWS_PER_IT) {
     const int lm = base + srow;
@@ -121,5 +155,60 @@ DEVINL void store_frags_staged_f32(const f32x4 (&acc)[FM][FN],
         &stage_f32[lm * SEGN + scol4]);
     __builtin_nontemporal_store(
         v, reinterpret_cast<f32x4*>(C + c_off + (long)m * N + n));
+    if constexpr (BMAX) {
+      const uint32_t o = group_max_u32<LPR>(
+          max(max(float_to_ordered(v[0]), float_to_ordered(v[1])),
+              max(float_to_ordered(v[2]), float_to_ordered(v[3]))));
+      if (lane % LPR == base / ROWS_PER_IT) mine = o;
+    }
   }
+  if constexpr (BMAX) {
+    const int m = m_base + (lane % LPR) * ROWS_PER_IT + srow;
+    bmax[(long)m * NB + n_base / SEGN] = ordered_to_float(mine);
+  }
+}
+
+// The guarded f32 epilogue plus block maxima as above, for partial
+// tiles: the maximum is over the block's valid columns (n < N) only, and
+// a block with none (n_base >= N) or a row m >= M writes nothing. A row's
+// 16 columns of a fragment sit in the 16 lanes of one DPP row; lane
+// 4*i + r of it keeps the maximum of fragment row (i, r).
+template <int FM, int FN>
+DEVINL void store_frags_guarded_bmax(const f32x4 (&acc)[FM][FN], float* C,
+                                     long c_off, const float* bias,
+                                     int m_base, int n_base, int M, int N,
+                                     int act, float alpha, int lane,
+                                     float* bmax, long NB) {
+  static_assert(FM == 4, "64 rows per wave, one maximum per lane");
+  constexpr int SEGN = FN * 16;
+  const int crow_base = (lane >> 4) * 4;
+  const int ccol = lane & 15;
+  uint32_t mine = 0;
+#pragma unroll
+  for (int i = 0; i < FM; ++i) {
+    uint32_t o[4] = {0u, 0u, 0u, 0u};   // below every non-NaN key
+#pragma unroll
+    for (int j = 0; j < FN; ++j) {
+      const int n = n_base + j * 16 + ccol;
+      const bool valid = n < N;
+      const float bv = (valid && bias) ? bias[n] : 0.0f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m_base + i * 16 + crow_base + r;
+        const float v = apply_act(alpha * acc[i][j][r] + bv, act);
+        if (valid) {
+          o[r] = max(o[r], float_to_ordered(v));
+          if (m < M) C[c_off + (long)m * N + n] = v;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const uint32_t g = group_max_u32<16>(o[r]);
+      if (ccol == i * 4 + r) mine = g;
+    }
+  }
+  const int m = m_base + (ccol >> 2) * 16 + crow_base + (ccol & 3);
+  if (m < M && n_base < N)
+    bmax[(long)m * NB + n_base / SEGN] = ordered_to_float(mine);
 }

@@ -88,6 +88,48 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor,
     return out.squeeze(0) if sq_a else out
 
 
+def gemm_bmax_width(M: int, N: int, K: int, G: int = 1) -> int:
+    """Columns per block maximum of gemm_nt_bmax at this shape (the
+    extension reports it: 64, or 32 at M <= 64), 0 when the shape is
+    not covered (the gemv and gemm8 routes)."""
+    if gemm_route(M, N, K, G) != "gemm":
+        return 0
+    return _ext.lib().infomesh_gemm_bmax_width(M, N, K, G)
+
+
+def gemm_nt_bmax(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
+                 out: torch.Tensor | None = None,
+                 bmax: torch.Tensor | None = None
+                 ) -> tuple[torch.Tensor, torch.Tensor, int] | None:
+    """gemm_nt(a [M,K], b [N,K], out_f32=True) that also returns the
+    block maxima of every score row: (scores [M,N] f32 — the bits
+    gemm_nt writes —, bmax [M, ceil(N/W)] f32, W), bmax[m, j] =
+    max(scores[m, j*W:(j+1)*W]) in the selector's order (-0.0 < +0.0).
+    None, with nothing launched, when gemm_bmax_width is 0."""
+    M, K = a.shape
+    N, Kb = b.shape
+    assert K == Kb and K % 32 == 0, f"shape mismatch {a.shape} x {b.shape}"
+    _check(a, torch.bfloat16, "A")
+    _check(b, torch.bfloat16, "B")
+    W = gemm_bmax_width(M, N, K)
+    if W == 0:
+        return None
+    NB = (N + W - 1) // W
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=torch.float32)
+    if bmax is None:
+        bmax = torch.empty((M, NB), device=a.device, dtype=torch.float32)
+    for t, shape, name in ((out, (M, N), "out"), (bmax, (M, NB), "bmax")):
+        _check(t, torch.float32, name)
+        assert t.shape == shape, f"{name} must be {shape}, got {t.shape}"
+    rc = _ext.lib().infomesh_gemm_bf16_nt_bmax(
+        a.data_ptr(), b.data_ptr(), out.data_ptr(), None, bmax.data_ptr(),
+        M, N, K, 1, M * K, N * K, M * N, ACT["none"], alpha,
+        _ext.stream_ptr())
+    assert rc == 0, "tile changed between gemm_bmax_width and the launch"
+    return out, bmax, W
+
+
 def dense_scores(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0,
                  out: torch.Tensor | None = None) -> torch.Tensor | None:
     """Streaming dense-score GEMM (densescore.hip): C[M,N] f32 =
@@ -324,6 +366,40 @@ class TopK:
                           vals.data_ptr(), idx.data_ptr(), B, N, k,
                           0 if ext_hist1 is None else ext_hist1.data_ptr(),
                           _ext.stream_ptr())
+        return vals, idx
+
+
+class TopKPruned:
+    """TopK for scores whose producer also wrote block maxima
+    (gemm_nt_bmax): same output contract, but it reads the [B, NB]
+    maxima and k blocks of W scores per row instead of streaming
+    [B, N] three times (infomesh_topk_pruned in csrc/topk.hip). Keeps
+    its workspace like TopK; one instance per captured graph."""
+
+    def __init__(self, device: torch.device | str = "cuda"):
+        self.device = torch.device(device)
+        self._ws: torch.Tensor | None = None
+
+    def __call__(self, scores: torch.Tensor, bmax: torch.Tensor, W: int,
+                 k: int) -> tuple[torch.Tensor, torch.Tensor]:
+        assert scores.dim() == 2
+        _check(scores, torch.float32, "scores")
+        _check(bmax, torch.float32, "bmax")
+        B, N = scores.shape
+        assert 1 <= k <= 1024 and W > 0
+        assert bmax.shape == (B, (N + W - 1) // W), \
+            f"bmax must be [B, ceil(N/W)], got {tuple(bmax.shape)}"
+        lib = _ext.lib()
+        nu32 = lib.infomesh_topk_pruned_workspace_u32(B, N, k, W)
+        if self._ws is None or self._ws.numel() < nu32:
+            self._ws = torch.empty(nu32, device=scores.device,
+                                   dtype=torch.int32)
+        self._ws[:lib.infomesh_topk_pruned_zero_u32(B)].zero_()
+        vals = torch.empty((B, k), device=scores.device, dtype=torch.float32)
+        idx = torch.empty((B, k), device=scores.device, dtype=torch.int32)
+        lib.infomesh_topk_pruned(
+            scores.data_ptr(), bmax.data_ptr(), W, self._ws.data_ptr(),
+            vals.data_ptr(), idx.data_ptr(), B, N, k, _ext.stream_ptr())
         return vals, idx
 
 

@@ -183,6 +183,59 @@ def masked_topk(scores: torch.Tensor, k: int, bits: torch.Tensor,
     return vals, idx
 
 
+def ordered_key(x: torch.Tensor) -> torch.Tensor:
+    """float_to_ordered of csrc/common.h as int64: the total order the
+    selector ranks f32 by (-0.0 just below +0.0, -inf lowest non-NaN)."""
+    bits = x.detach().float().cpu().contiguous().view(torch.int32) \
+        .to(torch.int64) & 0xFFFFFFFF
+    return torch.where(bits >= 0x80000000, bits ^ 0xFFFFFFFF,
+                       bits | 0x80000000)
+
+
+def block_max(scores: torch.Tensor, W: int) -> torch.Tensor:
+    """Oracle of the GEMM's block maxima: [B, N] f32 -> [B, ceil(N/W)],
+    the maximum in ordered_key order of every W consecutive columns
+    (the last block over its valid columns only), bit for bit."""
+    s = scores.detach().float().cpu()
+    B, N = s.shape
+    NB = (N + W - 1) // W
+    key = torch.full((B, NB * W), -1, dtype=torch.int64)
+    key[:, :N] = ordered_key(s)
+    pos = key.view(B, NB, W).argmax(dim=2)
+    cols = (pos + torch.arange(NB) * W).clamp(max=N - 1)
+    return s.gather(1, cols)
+
+
+def topk_pruned(scores: torch.Tensor, bmax: torch.Tensor, W: int,
+                k: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """Oracle of infomesh_topk_pruned, by the same steps: take the
+    min(k, NB) blocks with the largest maxima, and the top k of their
+    union in value order, equal values by ascending column. Rows with
+    fewer than k columns pad with -inf / -1."""
+    s = scores.detach().float().cpu()
+    B, N = s.shape
+    NB = (N + W - 1) // W
+    assert bmax.shape == (B, NB)
+    k1 = min(k, NB)
+    ids = torch.topk(ordered_key(bmax), k1, dim=1).indices.sort(dim=1).values
+    cols = (ids[:, :, None] * W + torch.arange(W)).reshape(B, k1 * W)
+    real = cols < N
+    cand = s.gather(1, cols.clamp(max=N - 1))
+    # padding ranks under everything, a real -inf included
+    key = torch.where(real, ordered_key(cand), torch.full_like(cols, -1))
+    # +-0.0 are one value when it comes to the order among equals
+    key = torch.where(key == 0x7FFFFFFF, key + 1, key)
+    order = torch.sort(key, dim=1, descending=True, stable=True).indices
+    kk = min(k, k1 * W)
+    order = order[:, :kk]
+    vals = torch.full((B, k), float("-inf"))
+    idx = torch.full((B, k), -1, dtype=torch.int64)
+    ok = real.gather(1, order)
+    vals[:, :kk] = torch.where(ok, cand.gather(1, order), vals[:, :kk])
+    idx[:, :kk] = torch.where(ok, cols.gather(1, order), idx[:, :kk])
+    return vals, idx
+
+
 def attn_decode(q: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, lens: torch.Tensor,
                 scale: float) -> torch.Tensor:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Dense-plane probe: time the scoring GEMM + top-k at flagship shapes.
 Round-1 baseline: 529 us at 128x1.25Mx384 (~3.1 TB/s effective) vs a
-~5.4 TB/s measured mixed ceiling (BACKLOG / VERDICT #6)."""
+~5.4 TB/s measured mixed ceiling (BACKLOG / VERDICT #6).
+--pruned times the pair the dense plane runs today instead: the GEMM
+that also writes block maxima and the selector that reads them."""
 from __future__ import annotations
 
 import argparse
@@ -21,6 +23,8 @@ def main() -> None:
     ap.add_argument("--dim", type=int, default=384)
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--pruned", action="store_true",
+                    help="GEMM with block maxima + pruned top-k")
     args = ap.parse_args()
     from infomesh_amd.ops import _build
     _build.build()
@@ -39,13 +43,42 @@ def main() -> None:
     err = (got[:4, :4096] - ref).abs().max().item()
     print(f"parity max err (4x4096 slice): {err:.4f}")
 
-    for name, fn in [
-        ("gemm", lambda: K.gemm_nt(a, b, out_f32=True, out=out)),
-        ("topk", lambda: tk(out.reshape(M, N), args.k)),
-        ("gemm+topk", lambda: tk(K.gemm_nt(a, b, out_f32=True,
-                                           out=out).reshape(M, N),
-                                 args.k)),
-    ]:
+    gemm_gb = (N * D * 2 + M * D * 2 + M * N * 4) / 1e9
+    if args.pruned:
+        W = K.gemm_bmax_width(M, N, D)
+        assert W, "shape has no block-maxima GEMM"
+        NB = (N + W - 1) // W
+        bmax = torch.empty(M, NB, device=dev, dtype=torch.float32)
+        tkp = K.TopKPruned(dev)
+        out2d = out.reshape(M, N)
+        K.gemm_nt_bmax(a, b, out=out2d, bmax=bmax)
+        assert torch.equal(bmax[:, :-1],
+                           out2d[:, :(NB - 1) * W].view(M, NB - 1, W)
+                           .amax(dim=2)), "block maxima differ"
+        # bytes moved: the GEMM writes the maxima once; the selector
+        # streams them three times (hist1, hist2, compact), reads
+        # min(k, NB) blocks of W scores and writes them side by side,
+        # and streams that copy three times — no term in M * N
+        bmax_gb = M * NB * 4 / 1e9
+        sel_gb = 3 * bmax_gb + 5 * M * min(args.k, NB) * W * 4 / 1e9
+        cases = [
+            ("gemm+bmax", gemm_gb + bmax_gb,
+             lambda: K.gemm_nt_bmax(a, b, out=out2d, bmax=bmax)),
+            ("topk pruned", sel_gb, lambda: tkp(out2d, bmax, W, args.k)),
+            ("gemm+bmax+topk pruned", gemm_gb + bmax_gb + sel_gb,
+             lambda: tkp(*K.gemm_nt_bmax(a, b, out=out2d, bmax=bmax),
+                         args.k)),
+        ]
+    else:
+        cases = [
+            ("gemm", gemm_gb, lambda: K.gemm_nt(a, b, out_f32=True, out=out)),
+            ("topk", 3 * M * N * 4 / 1e9,
+             lambda: tk(out.reshape(M, N), args.k)),
+            ("gemm+topk", (N * D * 2 + 4 * M * N * 4) / 1e9,
+             lambda: tk(K.gemm_nt(a, b, out_f32=True,
+                                  out=out).reshape(M, N), args.k)),
+        ]
+    for name, gb, fn in cases:
         for _ in range(5):
             fn()
         torch.cuda.synchronize()
@@ -56,12 +89,6 @@ def main() -> None:
         e1.record()
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / args.iters
-        if name == "gemm":
-            gb = (N * D * 2 + M * D * 2 + M * N * 4) / 1e9
-        elif name == "topk":
-            gb = 3 * M * N * 4 / 1e9
-        else:
-            gb = (N * D * 2 + 4 * M * N * 4) / 1e9
         print(f"{name}: {ms * 1e3:.0f} us  ({gb / (ms / 1e3):.2f} GB/s)")
 
 
