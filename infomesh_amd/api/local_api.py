@@ -73,10 +73,21 @@ def create_app(ctx: AppContext, api_key: str = "",
         return {"ready": ready, "engine": ctx.engine is not None}
 
     @app.get("/search")
-    def search(q: str, limit: int = 10, mode: str = "auto"):
+    def search(q: str, limit: int = 10, mode: str = "auto",
+               include_domains: str = "", exclude_domains: str = "",
+               recency_days: float = 0):
+        """include_domains / exclude_domains: comma-separated exact
+        domains to allow / block; recency_days: crawled that recently."""
         if not q.strip():
             raise HTTPException(400, "empty query")
-        resp = ctx.search(q, limit=min(limit, 50), mode=mode)
+        try:
+            resp = ctx.search(
+                q, limit=min(limit, 50), mode=mode,
+                include_domains=[d for d in include_domains.split(",") if d],
+                exclude_domains=[d for d in exclude_domains.split(",") if d],
+                recency_days=recency_days)
+        except ValueError as e:      # domain lists over the cap
+            raise HTTPException(400, str(e)) from e
         return {"query": q, "mode": resp.mode,
                 "elapsed_ms": round(resp.elapsed_ms, 2),
                 "results": [result_to_dict(r) for r in resp.results]}

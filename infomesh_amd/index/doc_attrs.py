@@ -21,6 +21,10 @@ from ..hashing import hash64
 LANG_MASK = 0xFFFF
 DEAD_BIT = 1 << 16      # attribute word 1
 HAS_SITE_BIT = 1 << 16  # predicate word z
+# bit 17 of z is the query plane's in-transit "row has a filter" mark
+HAS_ALLOW_BIT = 1 << 18  # predicate word z: an allow list goes with it
+HAS_BLOCK_BIT = 1 << 19  # predicate word z: a block list goes with it
+MAX_LIST_HASHES = 2048   # per predicate, allow and block together
 U32_MAX = 0xFFFFFFFF
 
 
@@ -65,17 +69,74 @@ class DocFilter:
     site: str | None = None
     after: float | None = None
     before: float | None = None
+    # domain lists, matched exactly on the stored (lower-cased) domain:
+    # with `sites` a document's domain must be one of them, and it must
+    # never be one of `exclude_sites` (a domain in both is blocked);
+    # `site` and `sites` together must both hold
+    sites: tuple[str, ...] = ()
+    exclude_sites: tuple[str, ...] = ()
+
+
+def _is_packed_sets(f) -> bool:
+    """(words4, allow_hashes, block_hashes), the form pack_pred_sets
+    returns and the query plane forwards between ranks."""
+    return isinstance(f, tuple) and len(f) == 3 and isinstance(f[0], tuple)
 
 
 def pack_pred(f) -> tuple[int, int, int, int]:
     """Predicate words (x, y, z, w) of a DocFilter; None is the
     live-only predicate. A 4-tuple is taken as words already packed
-    (the query plane forwards predicates between ranks in that form)."""
+    (the query plane forwards predicates between ranks in that form).
+    A filter with domain lists has no 4-word form: pack_pred_sets."""
     if f is None:
         return (0, U32_MAX, 0, 0)
-    if isinstance(f, tuple):
+    if isinstance(f, tuple) and not _is_packed_sets(f):
         x, y, z, w = (int(v) & U32_MAX for v in f)
         return (x, y, z, w)
+    words, allow, block = pack_pred_sets(f)
+    if allow or block:
+        raise ValueError("filter carries domain lists: use pack_pred_sets")
+    return words
+
+
+def _hash_list(domains) -> tuple[int, ...]:
+    """domain_hash of every name, unique, ascending as unsigned 32-bit."""
+    return tuple(sorted({domain_hash(d) for d in domains}))
+
+
+def pack_pred_sets(f) -> tuple[tuple[int, int, int, int],
+                               tuple[int, ...], tuple[int, ...]]:
+    """(words4, allow_hashes, block_hashes) of a filter with or without
+    domain lists. The hashes are domain_hash values, unique and sorted
+    ascending as unsigned 32-bit; bits 18 / 19 of word z say that the
+    allow / block list is non-empty. Accepts what pack_pred accepts and
+    its own result (which passes through). More than MAX_LIST_HASHES
+    hashes in the two lists together is a ValueError."""
+    if _is_packed_sets(f):
+        words, allow, block = f
+        allow = tuple(int(h) & U32_MAX for h in allow)
+        block = tuple(int(h) & U32_MAX for h in block)
+        words = pack_pred(words)
+    elif f is None or isinstance(f, tuple):
+        return pack_pred(f), (), ()
+    else:
+        allow, block = _hash_list(f.sites), _hash_list(f.exclude_sites)
+        words = _pack_words(f)
+    if len(allow) + len(block) > MAX_LIST_HASHES:
+        raise ValueError(
+            f"domain lists hold {len(allow) + len(block)} hashes; the cap "
+            f"is {MAX_LIST_HASHES} per predicate, allow and block together")
+    x, y, z, w = words
+    z &= ~(HAS_ALLOW_BIT | HAS_BLOCK_BIT)
+    if allow:
+        z |= HAS_ALLOW_BIT
+    if block:
+        z |= HAS_BLOCK_BIT
+    return (x, y, z, w), allow, block
+
+
+def _pack_words(f: DocFilter) -> tuple[int, int, int, int]:
+    """The four words of a DocFilter's non-list fields."""
     x = 0 if f.after is None else _clamp_u32(math.ceil(f.after))
     y = U32_MAX if f.before is None else _clamp_u32(math.floor(f.before))
     z = lang16(f.language)
@@ -91,9 +152,12 @@ def words_i32(rows) -> np.ndarray:
     return np.asarray(rows, dtype=np.uint32).reshape(-1, 4).view(np.int32)
 
 
-def passes(attrs: np.ndarray, pred) -> np.ndarray:
+def passes(attrs: np.ndarray, pred, allow=None, block=None) -> np.ndarray:
     """The predicate in numpy: attrs [N, 4] (int32 or uint32 bits), pred
-    4 words -> bool [N]. CpuShard and the bitmask oracle both use it."""
+    4 words -> bool [N]. CpuShard and the bitmask oracle both use it.
+    allow / block: u32 domain hashes (any int dtype with those bits); a
+    non-empty allow list must hold the document's w2, a block list must
+    not. As in the kernel, the lists' lengths decide, not the flag bits."""
     a = np.ascontiguousarray(attrs).view(np.uint32).reshape(-1, 4)
     x, y, z, w = (int(v) & U32_MAX for v in pred)
     qlang = z & LANG_MASK
@@ -103,4 +167,15 @@ def passes(attrs: np.ndarray, pred) -> np.ndarray:
         ok &= (a[:, 1] & np.uint32(LANG_MASK)) == np.uint32(qlang)
     if z & HAS_SITE_BIT:
         ok &= a[:, 2] == np.uint32(w)
+    if allow is not None and len(allow):
+        ok &= np.isin(a[:, 2], _as_u32(allow))
+    if block is not None and len(block):
+        ok &= ~np.isin(a[:, 2], _as_u32(block))
     return ok
+
+
+def _as_u32(hashes) -> np.ndarray:
+    h = np.asarray(hashes)
+    if h.dtype.itemsize == 4:
+        return np.ascontiguousarray(h).view(np.uint32)
+    return (h.astype(np.int64) & U32_MAX).astype(np.uint32)

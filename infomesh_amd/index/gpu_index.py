@@ -33,7 +33,8 @@ import numpy as np
 import torch
 
 from ..hashing import hash64
-from .doc_attrs import DEAD_BIT, DocFilter, pack_pred, passes, words_i32
+from .doc_attrs import (DEAD_BIT, DocFilter, pack_pred, pack_pred_sets, passes,
+                        words_i32)
 
 BM25_K1 = 1.2
 BM25_B = 0.75
@@ -570,8 +571,12 @@ class GpuShard:
     def _pred_rows(self, filters, B: int):
         """None when the mask is inactive (no filter in the batch and
         no tombstone in the shard), else (preds [P, 4] i32 host words,
-        row_pred [B] host i32) with the batch's predicates deduped;
-        a None filter is the live-only predicate."""
+        row_pred [B] host i32, lists) with the batch's predicates
+        deduped; a None filter is the live-only predicate. lists is
+        None when no predicate carries a domain list, else one
+        (allow_hashes, block_hashes) pair per predicate. A filter is a
+        DocFilter, packed words, or the (words, allow, block) form the
+        query plane forwards."""
         if self.n_dead == 0 and (filters is None
                                  or all(f is None for f in filters)):
             return None
@@ -579,8 +584,27 @@ class GpuShard:
             filters = [None] * B
         assert len(filters) == B, "one filter (or None) per query"
         seen: dict = {}
-        rows = [seen.setdefault(pack_pred(f), len(seen)) for f in filters]
-        return words_i32(list(seen)), np.asarray(rows, dtype=np.int32)
+        rows = [seen.setdefault(pack_pred_sets(f), len(seen))
+                for f in filters]
+        lists = None
+        if any(allow or block for _, allow, block in seen):
+            lists = [(allow, block) for _, allow, block in seen]
+        return (words_i32([words for words, _, _ in seen]),
+                np.asarray(rows, dtype=np.int32), lists)
+
+    @staticmethod
+    def _list_tables(lists) -> tuple[np.ndarray, np.ndarray]:
+        """Per-predicate (allow, block) hash tuples -> (desc [P, 4] i32,
+        doms flat i32 with the u32 bits) as filter_bitmask_sets reads
+        them."""
+        desc = np.zeros((len(lists), 4), dtype=np.int32)
+        flat: list[int] = []
+        for p, (allow, block) in enumerate(lists):
+            desc[p] = (len(flat), len(allow),
+                       len(flat) + len(allow), len(block))
+            flat.extend(allow)
+            flat.extend(block)
+        return desc, np.asarray(flat, dtype=np.uint32).view(np.int32)
 
     def _mask_for(self, filters: list[DocFilter | None] | None, B: int):
         """(bits [P, W] i32, row_pred [B] i32) on the device for the
@@ -589,7 +613,7 @@ class GpuShard:
         pr = self._pred_rows(filters, B)
         if pr is None:
             return None
-        preds, rows = pr
+        preds, rows, lists = pr
         cur = torch.cuda.current_stream(self.device)
         live_only = len(preds) == 1 and tuple(
             preds.view(np.uint32)[0]) == pack_pred(None)
@@ -599,6 +623,12 @@ class GpuShard:
             bits, ready = self._live_bits
             cur.wait_event(ready)
             bits.record_stream(cur)
+        elif lists is not None:
+            desc, doms = self._list_tables(lists)
+            bits = K.filter_bitmask_sets(
+                self.attrs, torch.from_numpy(preds).to(self.device),
+                torch.from_numpy(desc),
+                torch.from_numpy(doms).to(self.device))
         else:
             bits = K.filter_bitmask(
                 self.attrs, torch.from_numpy(preds).to(self.device))
@@ -980,9 +1010,13 @@ class CpuShard(GpuShard):
         pr = self._pred_rows(filters, B)
         if pr is None:
             return None
-        preds, rows = pr
+        preds, rows, lists = pr
         a = self.attrs.numpy()
-        ok = np.stack([passes(a, p) for p in preds.view(np.uint32)])
+        if lists is None:
+            lists = [((), ())] * len(preds)
+        ok = np.stack([passes(a, p, allow=allow, block=block)
+                       for p, (allow, block) in zip(preds.view(np.uint32),
+                                                    lists)])
         return torch.from_numpy(~ok[rows])
 
     @staticmethod

@@ -239,10 +239,14 @@ class LocalStore:
                domain: str | None = None,
                after: float | None = None,
                before: float | None = None,
-               match_any: bool = False) -> list[SearchHit]:
+               match_any: bool = False,
+               include_domains=None,
+               exclude_domains=None) -> list[SearchHit]:
         """FTS5 MATCH + bm25() ordering + snippet() with filters
         (reference: local_store.py:253-352). match_any=True ORs the
-        terms (fact-check / recall-first queries)."""
+        terms (fact-check / recall-first queries). include_domains /
+        exclude_domains: the stored domain must be IN / NOT IN the
+        list, compared exactly (lower-cased)."""
         fts_query = sanitize_fts_query(query, match_any=match_any)
         if not fts_query:
             return []
@@ -260,6 +264,12 @@ class LocalStore:
         if domain:
             sql.append(" AND d.domain = ?")
             params.append(domain.lower())
+        for op, names in ((" IN ", include_domains),
+                          (" NOT IN ", exclude_domains)):
+            names = sorted({n.lower() for n in names or ()})
+            if names:
+                sql.append(f" AND d.domain{op}({','.join('?' * len(names))})")
+                params.extend(names)
         if after is not None:
             sql.append(" AND d.crawled_at >= ?")
             params.append(after)
@@ -277,6 +287,30 @@ class LocalStore:
                           bm25=-float(r["rank"]),  # sqlite bm25() is negative
                           language=r["language"], domain=r["domain"],
                           crawled_at=r["crawled_at"]) for r in rows]
+
+    def domains_matching(self, names) -> list[str]:
+        """The stored domains that equal one of `names` or end in
+        "." + name (python.org admits docs.python.org, not
+        notpython.org), sorted. Turns a caller's suffix semantics into
+        the exact names the domain lists compare."""
+        names = sorted({n.strip().lower() for n in names or ()
+                        if n and n.strip()})
+        if not names:
+            return []
+        found: set[str] = set()
+        for lo in range(0, len(names), 400):    # bound variables: 2 a name
+            where, params = [], []
+            for n in names[lo:lo + 400]:
+                # the suffix is text, not a pattern: escape LIKE's wildcards
+                literal = (n.replace("\\", "\\\\").replace("%", "\\%")
+                           .replace("_", "\\_"))
+                where.append(
+                    "domain = ? OR domain LIKE '%.' || ? ESCAPE '\\'")
+                params += [n, literal]
+            found.update(r["domain"] for r in self.conn.execute(
+                "SELECT DISTINCT domain FROM documents WHERE "
+                + " OR ".join(where), params))
+        return sorted(found)
 
     def suggest(self, prefix: str, limit: int = 5) -> list[str]:
         """Title-prefix suggestions (reference: local_store.py:354).

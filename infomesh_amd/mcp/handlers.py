@@ -8,10 +8,12 @@ post-processing).
 from __future__ import annotations
 
 import asyncio
+import logging
 import time
 from typing import Any
 
 from ..errors import InfoMeshError, format_error
+from ..index.doc_attrs import MAX_LIST_HASHES
 from ..search.explain import explain_search
 from ..search.formatter import result_to_dict
 from ..search.nlp import did_you_mean
@@ -19,6 +21,7 @@ from ..search.rag import format_rag_output, extract_answer
 from ..services import AppContext
 
 CRAWL_RATE_PER_HOUR = 60
+log = logging.getLogger("infomesh.mcp")
 
 
 class Handlers:
@@ -65,10 +68,33 @@ class Handlers:
                         trust_fn=self.ctx.trust.trust_fn(),
                         boost_fn=(self.ctx.feedback.url_boost
                                   if self.ctx.feedback else None))}
-        over = limit * 2 if (domain_allowlist or domain_blocklist
-                             or recency_days) else limit
-        resp = self.ctx.search(query, limit=over, mode=mode)
+        # Domain lists and recency are applied inside the search (the
+        # GPU plane's masked top-k or the store's SQL), so `limit` hits
+        # are the true top of the passing documents. The lists keep
+        # their suffix semantics (python.org admits docs.python.org):
+        # the store expands each name to the exact domains it holds.
+        include = exclude = None
+        if domain_allowlist:
+            # nothing stored under an allowed name: keep the names, which
+            # then match nothing, rather than lift the restriction
+            include = (self.ctx.store.domains_matching(domain_allowlist)
+                       or list(domain_allowlist))
+        if domain_blocklist:
+            exclude = self.ctx.store.domains_matching(domain_blocklist)
+        if len(include or ()) + len(exclude or ()) > MAX_LIST_HASHES:
+            log.warning(
+                "web_search: %d domains after expansion, over the cap of "
+                "%d; over-fetching and filtering the hits instead",
+                len(include or ()) + len(exclude or ()), MAX_LIST_HASHES)
+            resp = self.ctx.search(query, limit=limit * 2, mode=mode)
+        else:
+            resp = self.ctx.search(query, limit=limit, mode=mode,
+                                   include_domains=include,
+                                   exclude_domains=exclude,
+                                   recency_days=recency_days)
         results = [result_to_dict(r) for r in resp.results]
+        # the post-filter stays as a guard; it drops nothing the search
+        # already filtered
         if domain_allowlist or domain_blocklist or recency_days:
             from urllib.parse import urlparse
             import time as _t

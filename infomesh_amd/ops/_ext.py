@@ -46,6 +46,8 @@ _SIGNATURES: dict[str, list] = {
                              c_void_p],
     "infomesh_filter_bitmask": [c_void_p, c_void_p, c_void_p, c_long,
                                 c_int, c_void_p],
+    "infomesh_filter_bitmask_sets": [c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_long, c_int, c_void_p],
     "infomesh_topk_workspace_u32": [c_int],
     "infomesh_topk_zero_u32": [c_int],
     "infomesh_bm25_block": [c_void_p, c_void_p, c_void_p, c_void_p,

@@ -426,6 +426,46 @@ def filter_bitmask(attrs: torch.Tensor, preds: torch.Tensor) -> torch.Tensor:
     return bits
 
 
+FILTER_SETS_MAX = 2048   # hashes per predicate the kernel stages in LDS
+
+
+def filter_bitmask_sets(attrs: torch.Tensor, preds: torch.Tensor,
+                        desc: torch.Tensor, doms: torch.Tensor
+                        ) -> torch.Tensor:
+    """filter_bitmask with per-predicate domain lists: desc [P, 4] i32
+    (allow_off, allow_n, block_off, block_n, offsets into doms) and doms
+    the flat i32 array of u32 domain hashes, each list unique and
+    ascending as unsigned (index/doc_attrs.pack_pred_sets). Same output.
+
+    The descriptors are checked here, on the host, before the kernel
+    indexes doms with them: hand desc over as a host tensor (it is then
+    uploaded, no sync) or as a device tensor (copied back to check)."""
+    _check(attrs, torch.int32, "attrs")
+    _check(preds, torch.int32, "preds")
+    assert attrs.dim() == 2 and attrs.shape[1] == 4
+    assert preds.dim() == 2 and preds.shape[1] == 4 and preds.shape[0] >= 1
+    N, P = attrs.shape[0], preds.shape[0]
+    assert P <= 65535
+    assert desc.dtype == torch.int32 and desc.shape == (P, 4) \
+        and desc.is_contiguous(), "desc: contiguous [P, 4] i32"
+    _check(doms, torch.int32, "doms")
+    assert doms.dim() == 1
+    h = desc.cpu()
+    off, n = h[:, 0::2].long(), h[:, 1::2].long()
+    assert bool((n >= 0).all()) and bool((off >= 0).all()) \
+        and bool((off + n <= doms.numel()).all()), "desc points outside doms"
+    assert int(n.sum(1).max()) <= FILTER_SETS_MAX, \
+        f"more than {FILTER_SETS_MAX} hashes in one predicate's lists"
+    if not desc.is_cuda:
+        desc = desc.to(attrs.device, non_blocking=True)
+    W = (N + 63) // 64 * 2
+    bits = torch.empty((P, W), device=attrs.device, dtype=torch.int32)
+    _ext.lib().infomesh_filter_bitmask_sets(
+        attrs.data_ptr(), preds.data_ptr(), desc.data_ptr(),
+        doms.data_ptr(), bits.data_ptr(), N, P, _ext.stream_ptr())
+    return bits
+
+
 def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
                qt_off: torch.Tensor, qt_ut: torch.Tensor,
                qt_idf: torch.Tensor, u_begin: torch.Tensor,

@@ -166,6 +166,27 @@ def filter_bitmask(attrs: torch.Tensor, preds: torch.Tensor) -> torch.Tensor:
     return torch.from_numpy(np.stack(rows).view(np.int32).reshape(-1, W))
 
 
+def filter_bitmask_sets(attrs: torch.Tensor, preds: torch.Tensor,
+                        desc: torch.Tensor, doms: torch.Tensor
+                        ) -> torch.Tensor:
+    """Oracle of filter_bitmask_sets: filter_bitmask plus, per predicate,
+    the allow list doms[allow_off : allow_off + allow_n] and the block
+    list doms[block_off : block_off + block_n] of desc [P, 4]."""
+    import numpy as np
+    from ..index.doc_attrs import passes
+    a = attrs.cpu().numpy()
+    h = doms.cpu().numpy().view(np.uint32)
+    N = a.shape[0]
+    W = (N + 63) // 64 * 2
+    rows = []
+    for pred, (ao, an, bo, bn) in zip(preds.cpu().numpy().view(np.uint32),
+                                      desc.cpu().numpy().tolist()):
+        ok = np.zeros(W * 32, dtype=bool)
+        ok[:N] = passes(a, pred, allow=h[ao:ao + an], block=h[bo:bo + bn])
+        rows.append(np.packbits(ok, bitorder="little").view(np.uint32))
+    return torch.from_numpy(np.stack(rows).view(np.int32).reshape(-1, W))
+
+
 def masked_topk(scores: torch.Tensor, k: int, bits: torch.Tensor,
                 row_pred: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Oracle of the masked top-k: failing columns become -inf, then

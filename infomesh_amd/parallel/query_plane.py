@@ -18,7 +18,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ..index.doc_attrs import U32_MAX, pack_pred
+from ..index.doc_attrs import (HAS_ALLOW_BIT, HAS_BLOCK_BIT, U32_MAX,
+                               pack_pred_sets)
 from ..index.gpu_index import GpuShard, ShardHits
 from .fabric import Fabric
 
@@ -27,9 +28,12 @@ MAX_QUERY_TERMS = 32
 # Filter predicates ride in the terms broadcast as two extra int64
 # columns per row: x | y<<32 and z | w<<32 of doc_attrs.pack_pred. Bit 17
 # of z is unused by the predicate and marks "this row has a filter";
-# an unfiltered row carries two zeros.
+# an unfiltered row carries two zeros. Bits 18 / 19 of z (has_allow /
+# has_block) announce domain lists; only a batch with such a row is
+# followed by the two list broadcasts of _broadcast_lists.
 _PRED_COLS = 2
 _HAS_FILTER = 1 << 17
+_HAS_LISTS = HAS_ALLOW_BIT | HAS_BLOCK_BIT
 
 
 @dataclass
@@ -388,6 +392,7 @@ class DistributedQueryPlane:
         T = MAX_QUERY_TERMS
         terms_t = torch.full((B, T + _PRED_COLS), -1, dtype=torch.int64)
         terms_t[:, T:] = 0
+        lists: dict = {}      # row -> (allow, block), rank 0 only
         if queries_terms is not None:
             for i, t in enumerate(queries_terms):
                 t = t[:T]
@@ -397,8 +402,10 @@ class DistributedQueryPlane:
                 for i, f in enumerate(filters):
                     if f is None:
                         continue
-                    x, y, z, w = pack_pred(f)
+                    (x, y, z, w), allow, block = pack_pred_sets(f)
                     cols[i] = (x | (y << 32), z | _HAS_FILTER | (w << 32))
+                    if allow or block:
+                        lists[i] = (allow, block)
                 terms_t[:, T:] = torch.from_numpy(cols.view(np.int64))
         terms_t = terms_t.to(dev)
         self.fabric.broadcast(terms_t)
@@ -412,7 +419,39 @@ class DistributedQueryPlane:
                  int(c1) & U32_MAX & ~_HAS_FILTER, int(c1) >> 32)
                 if h else None
                 for (c0, c1), h in zip(cols, has)]
+            if (cols[:, 1] & np.uint64(_HAS_LISTS)).any():
+                # every rank read the same flag bits, so all of them
+                # take this branch together
+                self._broadcast_lists(filters, lists, B)
         return [tt[i, :T][tt[i, :T] >= 0] for i in range(B)], filters
+
+    def _broadcast_lists(self, filters: list, lists: dict, B: int) -> None:
+        """The domain lists of a batch whose flag bits announce some:
+        one fixed-shape [B, 2] count broadcast (allow_n, block_n per
+        row), then one flat broadcast of all the hashes, rows in order,
+        allow before block. Rewrites the listed rows of `filters` from
+        packed words to (words, allow, block), on every rank alike."""
+        dev = self.fabric.device
+        counts = torch.zeros((B, 2), dtype=torch.int64)
+        for i, (allow, block) in lists.items():
+            counts[i, 0], counts[i, 1] = len(allow), len(block)
+        counts = counts.to(dev)
+        self.fabric.broadcast(counts)
+        counts = counts.cpu().numpy()
+        flat = torch.zeros(int(counts.sum()), dtype=torch.int64)
+        if lists:
+            flat = torch.tensor(
+                [h for i in sorted(lists) for part in lists[i] for h in part],
+                dtype=torch.int64)
+        flat = flat.to(dev)
+        self.fabric.broadcast(flat)
+        hashes = flat.cpu().tolist()
+        at = 0
+        for i, (an, bn) in enumerate(counts.tolist()):
+            if an or bn:
+                filters[i] = (filters[i], tuple(hashes[at:at + an]),
+                              tuple(hashes[at + an:at + an + bn]))
+                at += an + bn
 
     def _get_scores_buf(self, B: int) -> torch.Tensor | None:
         N = self.shard.n_docs

@@ -12,6 +12,20 @@ import httpx
 DEFAULT_BASE = "http://127.0.0.1:8080"
 
 
+def _search_params(query, limit, mode, include_domains, exclude_domains,
+                   recency_days) -> dict[str, Any]:
+    """/search parameters; the domain lists go comma-separated, and only
+    when given."""
+    params: dict[str, Any] = {"q": query, "limit": limit, "mode": mode}
+    if include_domains:
+        params["include_domains"] = ",".join(include_domains)
+    if exclude_domains:
+        params["exclude_domains"] = ",".join(exclude_domains)
+    if recency_days:
+        params["recency_days"] = recency_days
+    return params
+
+
 class InfoMeshClient:
     def __init__(self, base_url: str = DEFAULT_BASE, api_key: str = "",
                  timeout: float = 30.0,
@@ -20,10 +34,14 @@ class InfoMeshClient:
         self._client = httpx.Client(base_url=base_url, headers=headers,
                                     timeout=timeout, transport=transport)
 
-    def search(self, query: str, limit: int = 10,
-               mode: str = "auto") -> list[dict[str, Any]]:
-        r = self._client.get("/search",
-                             params={"q": query, "limit": limit, "mode": mode})
+    def search(self, query: str, limit: int = 10, mode: str = "auto",
+               include_domains=None, exclude_domains=None,
+               recency_days: float = 0) -> list[dict[str, Any]]:
+        """include_domains / exclude_domains: exact domains to allow /
+        block; recency_days: only documents crawled that recently."""
+        r = self._client.get("/search", params=_search_params(
+            query, limit, mode, include_domains, exclude_domains,
+            recency_days))
         r.raise_for_status()
         return r.json()["results"]
 
@@ -74,10 +92,12 @@ class AsyncInfoMeshClient:
                                          timeout=timeout,
                                          transport=transport)
 
-    async def search(self, query: str, limit: int = 10,
-                     mode: str = "auto") -> list[dict[str, Any]]:
-        r = await self._client.get(
-            "/search", params={"q": query, "limit": limit, "mode": mode})
+    async def search(self, query: str, limit: int = 10, mode: str = "auto",
+                     include_domains=None, exclude_domains=None,
+                     recency_days: float = 0) -> list[dict[str, Any]]:
+        r = await self._client.get("/search", params=_search_params(
+            query, limit, mode, include_domains, exclude_domains,
+            recency_days))
         r.raise_for_status()
         return r.json()["results"]
 

@@ -6,6 +6,7 @@ filter parsing site:/lang:/dates → ParsedQuery, related-search tracker).
 """
 from __future__ import annotations
 
+import math
 import re
 import time
 from collections import OrderedDict
@@ -132,13 +133,26 @@ class ParsedQuery:
     after: float | None = None
     before: float | None = None
     raw: str = ""
+    # domain lists, matched exactly on the stored domain: site:a.org,b.org
+    # allows only these, -site:a.org[,b.org] blocks them
+    sites: tuple[str, ...] = ()
+    exclude_sites: tuple[str, ...] = ()
 
 
-_FILTER_RE = re.compile(r"\b(site|lang|language|before|after):(\S+)", re.I)
+# a minus belongs to the filter only in front of site: at the start of a
+# token; anywhere else it stays in the text as it always did
+_FILTER_RE = re.compile(
+    r"(?:(?<!\S)(-)(?=site:))?\b(site|lang|language|before|after):(\S+)",
+    re.I)
 _DATE_FMTS = ("%Y-%m-%d", "%Y/%m/%d", "%Y-%m", "%Y")
 
 
 def _parse_date(text: str) -> float | None:
+    if text.startswith("@"):          # @<epoch seconds>
+        try:
+            return float(text[1:])
+        except ValueError:
+            return None
     for fmt in _DATE_FMTS:
         try:
             return time.mktime(time.strptime(text, fmt))
@@ -149,11 +163,19 @@ def _parse_date(text: str) -> float | None:
 
 def parse_query_filters(query: str) -> ParsedQuery:
     """Extract site:/lang:/before:/after: filters from the query text
-    (reference: nlp.py:911-971)."""
+    (reference: nlp.py:911-971). site: with two or more comma-separated
+    names is an allow list and -site: a block list (with_filter_tokens
+    writes both); dates also come as @<epoch seconds>."""
     pq = ParsedQuery(text=query, raw=query)
     def _sub(m: re.Match) -> str:
-        key, val = m.group(1).lower(), m.group(2)
-        if key == "site":
+        minus, key, val = m.group(1), m.group(2).lower(), m.group(3)
+        names = _site_names(val) if key == "site" else ()
+        if minus:
+            pq.exclude_sites += tuple(
+                n for n in names if n not in pq.exclude_sites)
+        elif key == "site" and "," in val:
+            pq.sites += tuple(n for n in names if n not in pq.sites)
+        elif key == "site":
             pq.site = val.lower().lstrip("www.") if val.startswith("www.") else val.lower()
         elif key in ("lang", "language"):
             pq.language = val.lower()[:2]
@@ -165,6 +187,37 @@ def parse_query_filters(query: str) -> ParsedQuery:
     pq.text = _FILTER_RE.sub(_sub, query).strip()
     pq.text = re.sub(r"\s{2,}", " ", pq.text)
     return pq
+
+
+def _site_names(val: str) -> tuple[str, ...]:
+    """The lower-cased names of a comma-separated site value, in order,
+    without repeats. Lists match the stored domain exactly, so a
+    leading www. stays."""
+    return tuple(dict.fromkeys(
+        n for n in (p.strip().lower() for p in val.split(",")) if n))
+
+
+def with_filter_tokens(query: str, include=(), exclude=(),
+                       after: float | None = None) -> str:
+    """`query` with the tokens appended that parse_query_filters reads
+    back as (sites, exclude_sites, after): the one writer of that
+    syntax. A one-name allow list is written with the name twice, since
+    one name alone is the site: form; white space and commas, which no
+    host name holds, turn into '_' so that such a name keeps its place
+    in the list and matches nothing."""
+    def names(domains) -> list[str]:
+        return list(_site_names(",".join(
+            re.sub(r"[\s,]+", "_", d.strip()) for d in domains or ()
+            if d and d.strip())))
+    inc, exc = names(include), names(exclude)
+    parts = [query]
+    if inc:
+        parts.append("site:" + ",".join(inc * 2 if len(inc) == 1 else inc))
+    if exc:
+        parts.append("-site:" + ",".join(exc))
+    if after is not None:
+        parts.append(f"after:@{int(math.ceil(after))}")
+    return " ".join(parts)
 
 
 # ---------------------------------------------------- related searches

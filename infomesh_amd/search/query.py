@@ -65,14 +65,18 @@ def search_local(store: LocalStore, query: str, limit: int = 10,
     pq = parse_query_filters(query)
     eff = preprocess_query(pq.text)
     hits = store.search(eff, limit=limit * 2, language=pq.language,
-                        domain=pq.site, after=pq.after, before=pq.before)
+                        domain=pq.site, after=pq.after, before=pq.before,
+                        include_domains=pq.sites,
+                        exclude_domains=pq.exclude_sites)
     expanded: list[str] = []
     if len(hits) < max(3, limit // 2):
         # Sparse results → synonym expansion (query.py:136-156).
         for alt in expand_query(eff):
             expanded.append(alt)
             more = store.search(alt, limit=limit, language=pq.language,
-                                domain=pq.site, after=pq.after, before=pq.before)
+                                domain=pq.site, after=pq.after, before=pq.before,
+                                include_domains=pq.sites,
+                                exclude_domains=pq.exclude_sites)
             seen = {h.url for h in hits}
             hits.extend(h for h in more if h.url not in seen)
             if len(hits) >= limit:

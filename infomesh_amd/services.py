@@ -23,12 +23,13 @@ from .crawler.scheduler import Scheduler
 from .crawler.worker import CrawlResult, CrawlWorker
 from .engine import HybridEngine
 from .errors import GpuExtensionMissing, InfoMeshError
-from .index.doc_attrs import DocFilter
+from .index.doc_attrs import DocFilter, pack_pred_sets
 from .index.link_graph import LinkGraph
 from .index.local_store import Document, LocalStore
 from .search.batcher import QueryBatcher
 from .search.cache import QueryCache
-from .search.nlp import RelatedSearchTracker, parse_query_filters
+from .search.nlp import (RelatedSearchTracker, parse_query_filters,
+                         with_filter_tokens)
 from .search.passage import fast_snippet
 from .search.query import (SearchResponse, preprocess_query,
                            search_hybrid, search_local)
@@ -264,11 +265,28 @@ class AppContext:
     # ------------------------------------------------------------ search
     def search(self, query: str, limit: int | None = None,
                mode: str = "auto", use_cache: bool = True,
-               deduct: bool = True) -> SearchResponse:
+               deduct: bool = True, include_domains=None,
+               exclude_domains=None,
+               recency_days: float = 0) -> SearchResponse:
         """Unified search entry (reference mcp/handlers.py:382 flow):
-        cache -> credits -> local/hybrid/distributed -> cache."""
+        cache -> credits -> local/hybrid/distributed -> cache.
+
+        include_domains / exclude_domains: exact stored domains to
+        allow / block (the reference's include_domains / exclude_domains);
+        recency_days: only documents crawled that recently, to the
+        minute. All three travel as filter tokens in the query text, so
+        they reach the cache key and whichever path serves the query.
+        On the GPU plane one query's lists hold at most
+        doc_attrs.MAX_LIST_HASHES domains; more is a ValueError."""
         from .utils.plugins import GLOBAL_PLUGINS
         query = GLOBAL_PLUGINS.run("pre_search", query, mode=mode)
+        if include_domains or exclude_domains or recency_days:
+            after = None
+            if recency_days:
+                # whole minutes, so that repeats of a query share a key
+                after = (time.time() - float(recency_days) * 86400) // 60 * 60
+            query = with_filter_tokens(query, include_domains,
+                                       exclude_domains, after)
         limit = limit or self.config.search.max_results
         key = QueryCache.make_key(query, limit=limit, mode=mode)
         if use_cache:
@@ -287,9 +305,15 @@ class AppContext:
         # (reference local_store.py:253-352 filter SQL); gpu.filters
         # sends them to the engine's masked top-k instead.
         pq = parse_query_filters(query)
-        has_filters = bool(pq.site or pq.after or pq.before or pq.language)
+        has_filters = bool(pq.site or pq.after or pq.before or pq.language
+                           or pq.sites or pq.exclude_sites)
         if self.config.gpu.filters:
             has_filters = False
+            if engine_ready and mode != "local":
+                # over the cap: fail this caller here, not the whole
+                # batch inside the batcher's executor
+                pack_pred_sets(DocFilter(sites=pq.sites,
+                                         exclude_sites=pq.exclude_sites))
         if mode == "local" or (mode == "auto" and not engine_ready):
             resp = search_local(self.store, query, limit=limit,
                                 authority_fn=authority, trust_fn=trust_fn,
@@ -344,12 +368,19 @@ class AppContext:
                        limit: int) -> list[list]:
         """Batcher executor: ONE plane call + ONE hydration round trip
         for the whole batch (engine hits carry only global doc ids +
-        fused scores; url/title/domain/snippet come from LocalStore)."""
+        fused scores; url/title/domain/snippet come from LocalStore).
+
+        The GPU plane compares 32-bit domain hashes, so a hydrated hit
+        is checked against the query's domain filters by name and
+        dropped when its stored domain contradicts them. For site: that
+        is a curiosity; for a 2048-entry list against ~1M distinct
+        domains it is an expected event (2048 * 1M / 2^32 ~ 0.5 false
+        matches per query), so the guard covers the lists too."""
         if self.batcher is not None \
                 and self.batcher.engine is not self.engine:
             self.batcher.engine = self.engine   # engine was rebound
         filters = None
-        sites: list[str | None] = [None] * len(queries)
+        parsed: list = [None] * len(queries)
         if self.config.gpu.filters:
             # filter tokens travel inside the query text (the batcher's
             # signature knows nothing of them): split them off here,
@@ -357,23 +388,27 @@ class AppContext:
             parsed = [parse_query_filters(q) for q in queries]
             filters = [
                 DocFilter(language=pq.language, site=pq.site,
-                          after=pq.after, before=pq.before)
-                if (pq.site or pq.language or pq.after or pq.before)
+                          after=pq.after, before=pq.before,
+                          sites=pq.sites, exclude_sites=pq.exclude_sites)
+                if (pq.site or pq.language or pq.after or pq.before
+                    or pq.sites or pq.exclude_sites)
                 else None for pq in parsed]
             queries = [pq.text for pq in parsed]
-            sites = [pq.site for pq in parsed]
         per_q = self.engine.search_many(queries, limit=limit,
                                         filters=filters)
         gids = [h.doc_id for hits in per_q for h in hits]
         docs = self.store.get_documents(gids)
         out: list[list] = []
-        for q, hits, site in zip(queries, per_q, sites):
+        for q, hits, pq in zip(queries, per_q, parsed):
             hydrated = []
             for h in hits:
                 doc = docs.get(h.doc_id)
                 if doc is None:
                     continue
-                if site and doc.domain != site:
+                if pq is not None and (
+                        (pq.site and doc.domain != pq.site)
+                        or (pq.sites and doc.domain not in pq.sites)
+                        or doc.domain in pq.exclude_sites):
                     continue   # 32-bit domain-hash collision guard
                 h.url, h.title = doc.url, doc.title
                 h.domain, h.crawled_at = doc.domain, doc.crawled_at
