@@ -88,6 +88,10 @@ class GpuConfig:
     # site:/lang:/after:/before: queries run on the GPU plane (masked
     # top-k) instead of the FTS5 path
     filters: bool = False
+    # +word / -word in a query require / exclude the word, on the GPU
+    # plane (term operands in the masked top-k) and on the FTS5 path
+    # (NOT); off, the signs are plain text as they always were
+    term_operators: bool = False
 
 
 @dataclass(frozen=True)

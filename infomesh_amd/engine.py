@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from .index.doc_attrs import DocFilter, pack_attrs
+from .index.doc_attrs import DocFilter, TermOps, pack_attrs
 from .index.gpu_index import CpuShard, GpuShard, bm25_term_ids
 from .index.local_store import (Document, LocalStore, SearchHit,
                                 extract_domain)
@@ -185,25 +185,70 @@ class HybridEngine:
     # ------------------------------------------------------------ search
     def search(self, query: str, limit: int = 10,
                use_dense: bool | None = None,
-               filter: DocFilter | None = None) -> list[SearchHit]:
-        """Single-query search against the engine (shard-fused)."""
+               filter: DocFilter | None = None,
+               require: tuple[str, ...] | None = None,
+               exclude: tuple[str, ...] | None = None) -> list[SearchHit]:
+        """Single-query search against the engine (shard-fused).
+        require / exclude: words as in search_many."""
         return self.search_many(
             [query], limit=limit, use_dense=use_dense,
-            filters=None if filter is None else [filter])[0]
+            filters=None if filter is None else [filter],
+            require=None if require is None else [require],
+            exclude=None if exclude is None else [exclude])[0]
+
+    @staticmethod
+    def term_ops_for(query: str, require, exclude
+                     ) -> tuple[str, TermOps | None]:
+        """(text to score and embed, TermOps or None) of one query.
+        The words go through bm25_term_ids like document text
+        (tokenizer plugin, diacritic folding, CJK bigrams), and every
+        resulting id is an operand. Required words missing from the
+        query text are appended to it, so they are scored and embedded;
+        excluded words never are. Over doc_attrs.TERM_OPS_MAX operands
+        is a ValueError."""
+        require = tuple(w for w in require or () if w and w.strip())
+        exclude = tuple(w for w in exclude or () if w and w.strip())
+        if not require and not exclude:
+            return query, None
+        req_ids: list[int] = []
+        have = set(bm25_term_ids(query).tolist())
+        for w in require:
+            ids = bm25_term_ids(w).tolist()
+            if not set(ids) <= have:
+                query = f"{query} {w}".strip()
+                have |= set(ids)
+            req_ids += ids
+        exc_ids = [i for w in exclude for i in bm25_term_ids(w).tolist()]
+        return query, TermOps.of(req_ids, exc_ids) or None
 
     def search_many(self, queries: list[str], limit: int = 10,
                     use_dense: bool | None = None,
-                    filters: list[DocFilter | None] | None = None
+                    filters: list[DocFilter | None] | None = None,
+                    require: list[tuple[str, ...] | None] | None = None,
+                    exclude: list[tuple[str, ...] | None] | None = None
                     ) -> list[list[SearchHit]]:
         """Batched search: ONE collective plane.search_batch for the
         whole list (the batcher's execute path). Fusion happens exactly
         once, on the plane (RRF of the per-shard BM25 + dense top-k);
         callers hydrate url/title from the LocalStore. filters: one
         DocFilter or None per query, applied inside the shards' top-k
-        selection."""
+        selection. require / exclude: one tuple of words (or None) per
+        query; a hit holds every required word and no excluded one, on
+        both planes (term_ops_for says how words become operands)."""
         if self.shard.n_docs == 0 or not queries:
             return [[] for _ in queries]
         B = len(queries)
+        term_ops = None
+        if require is not None or exclude is not None:
+            require = require or [None] * B
+            exclude = exclude or [None] * B
+            assert len(require) == B and len(exclude) == B, \
+                "one tuple of words (or None) per query"
+            pairs = [self.term_ops_for(q, r, e)
+                     for q, r, e in zip(queries, require, exclude)]
+            queries = [q for q, _ in pairs]
+            if any(t is not None for _, t in pairs):
+                term_ops = [t for _, t in pairs]
         # pad the batch to a power-of-two bucket: the plane's hipGraph
         # cache, scores buffers and the encoder graphs are per-(B, k)
         # shape — unbounded serving batch sizes would thrash them
@@ -222,10 +267,12 @@ class HybridEngine:
             assert len(filters) == B, "one filter (or None) per query"
             filters = (list(filters) + [None] * (Bp - B)
                        if any(f is not None for f in filters) else None)
+        if term_ops is not None:
+            term_ops = term_ops + [None] * (Bp - B)
         fused = self.plane.search_batch(
             terms, emb, B=Bp, dim=emb.shape[1] if emb is not None else 384,
             n_results=limit, use_dense=use_dense and emb is not None,
-            filters=filters)
+            filters=filters, term_ops=term_ops)
         if fused is None:
             return [[] for _ in queries]
         ids = fused.ids.tolist()

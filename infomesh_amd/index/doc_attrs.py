@@ -77,6 +77,43 @@ class DocFilter:
     exclude_sites: tuple[str, ...] = ()
 
 
+TERM_OPS_MAX = 16   # operands per query row, require and exclude together
+
+
+@dataclass(frozen=True)
+class TermOps:
+    """A query row's required and excluded terms (+word / -word), as
+    hashed BM25 term ids (gpu_index.bm25_term_ids). A document passes
+    iff it holds EVERY require id and NO exclude id; both planes select
+    among the passing documents only (layout and kernel:
+    ops/csrc/termmask.hip).
+
+    A require id that occurs nowhere in the shard fails every document
+    (the row pads with -inf / -1), and an id in both lists passes
+    nothing. Build one with TermOps.of, which dedupes; more than
+    TERM_OPS_MAX operands in the two lists together is a ValueError."""
+    require: tuple[int, ...] = ()
+    exclude: tuple[int, ...] = ()
+
+    def __post_init__(self):
+        n = len(self.require) + len(self.exclude)
+        if n > TERM_OPS_MAX:
+            raise ValueError(
+                f"{n} term operands; the cap is {TERM_OPS_MAX} per query, "
+                f"required and excluded together")
+        if any(t < 0 for t in self.require + self.exclude):
+            raise ValueError("term ids are non-negative")
+
+    @classmethod
+    def of(cls, require=(), exclude=()) -> "TermOps":
+        """From any iterables of ids: each list deduped, order kept."""
+        return cls(tuple(dict.fromkeys(int(t) for t in require)),
+                   tuple(dict.fromkeys(int(t) for t in exclude)))
+
+    def __bool__(self) -> bool:
+        return bool(self.require or self.exclude)
+
+
 def _is_packed_sets(f) -> bool:
     """(words4, allow_hashes, block_hashes), the form pack_pred_sets
     returns and the query plane forwards between ranks."""

@@ -33,8 +33,8 @@ import numpy as np
 import torch
 
 from ..hashing import hash64
-from .doc_attrs import (DEAD_BIT, DocFilter, pack_pred, pack_pred_sets, passes,
-                        words_i32)
+from .doc_attrs import (DEAD_BIT, DocFilter, TermOps, pack_pred,
+                        pack_pred_sets, passes, words_i32)
 
 BM25_K1 = 1.2
 BM25_B = 0.75
@@ -606,11 +606,71 @@ class GpuShard:
             flat.extend(block)
         return desc, np.asarray(flat, dtype=np.uint32).view(np.int32)
 
-    def _mask_for(self, filters: list[DocFilter | None] | None, B: int):
+    @staticmethod
+    def _term_rows(term_ops, B: int) -> list[tuple[int, TermOps]]:
+        """(query row, its TermOps) of every row that has an operand."""
+        if term_ops is None:
+            return []
+        assert len(term_ops) == B, "one TermOps (or None) per query"
+        return [(i, t) for i, t in enumerate(term_ops) if t]
+
+    def _term_table(self, ops: list[TermOps]):
+        """The operand table of csrc/termmask.hip for these rows:
+        (op_off [R+1] i32, op_kind [T] i32, ids [T] i64), host arrays;
+        a row's require operands come before its exclude operands."""
+        op_off = np.zeros(len(ops) + 1, dtype=np.int32)
+        np.cumsum([len(t.require) + len(t.exclude) for t in ops],
+                  out=op_off[1:])
+        ids = np.asarray([i for t in ops for i in t.require + t.exclude],
+                         dtype=np.int64)
+        kind = np.asarray([k for t in ops for k in
+                           [0] * len(t.require) + [1] * len(t.exclude)],
+                          dtype=np.int32)
+        assert (ids < self.vocab).all(), "term id outside the vocabulary"
+        return op_off, kind, ids
+
+    def _mask_for(self, filters: list[DocFilter | None] | None, B: int,
+                  term_ops: list[TermOps | None] | None = None):
         """(bits [P, W] i32, row_pred [B] i32) on the device for the
-        masked top-k, or None when the mask is inactive."""
+        masked top-k, or None when the mask is inactive. Rows with term
+        operands get a bit row of their own, appended after the P
+        predicate rows: their predicate's bits with the documents
+        cleared that termmask.hip fails."""
+        trows = self._term_rows(term_ops, B)
+        mask = self._filter_mask_for(filters, B, force=bool(trows))
+        if mask is None:
+            return None
+        bits, h_rows = mask
+        if not trows:
+            return bits, torch.from_numpy(h_rows).to(self.device)
+        from ..ops import kernels as K
+        op_off, kind, ids = self._term_table([t for _, t in trows])
+        segs = [(seg.doc_ids, seg.doc_base, seg.n_docs,
+                 torch.from_numpy(seg.h_offs[ids]),
+                 torch.from_numpy(seg.h_offs[ids + 1]))
+                for seg in self.segments]
+        qrows = np.asarray([i for i, _ in trows], dtype=np.int64)
+        # a fresh [R, W] tensor: the (possibly cached) predicate rows
+        # are only read
+        term_bits = K.term_bitmask(
+            bits, torch.from_numpy(h_rows[qrows].astype(np.int64)), segs,
+            torch.from_numpy(op_off), torch.from_numpy(kind), self.n_docs)
+        h_rows = h_rows.copy()
+        h_rows[qrows] = bits.shape[0] + np.arange(len(trows), dtype=np.int32)
+        return (torch.cat([bits, term_bits]),
+                torch.from_numpy(h_rows).to(self.device))
+
+    def _filter_mask_for(self, filters, B: int, force: bool = False):
+        """(bits [P, W] i32 on the device, row_pred [B] i32 on the
+        host) of the batch's filters and the shard's tombstones, or
+        None when that mask is inactive. force: build it all the same
+        (live-only rows), for a batch that needs bit rows to start
+        from."""
         from ..ops import kernels as K
         pr = self._pred_rows(filters, B)
+        if pr is None and force:
+            pr = (words_i32([pack_pred(None)]), np.zeros(B, dtype=np.int32),
+                  None)
         if pr is None:
             return None
         preds, rows, lists = pr
@@ -636,7 +696,7 @@ class GpuShard:
                 ready = torch.cuda.Event()
                 ready.record(cur)
                 self._live_bits = (bits, ready)
-        return bits, torch.from_numpy(rows).to(self.device)
+        return bits, rows
 
     def hbm_bytes(self) -> int:
         total = sum(s.hbm_bytes() for s in self.segments)
@@ -742,7 +802,7 @@ class GpuShard:
 
     def search_bm25(self, queries_terms: list[np.ndarray], k: int,
                     scores_buf: torch.Tensor | None = None,
-                    mark=None, filters=None, _mask=None
+                    mark=None, filters=None, _mask=None, term_ops=None
                     ) -> tuple[torch.Tensor, torch.Tensor]:
         """BM25 plane only (needs terms, not embeddings) — callable on a
         side stream to overlap with query encoding. One kernel launch
@@ -752,7 +812,10 @@ class GpuShard:
         filters: one DocFilter or None per query. With a filter in the
         batch or a tombstone in the shard the select is masked: the
         fused pass-1 histogram counts failing documents, so it is not
-        produced and the masked top-k streams the matrix once more."""
+        produced and the masked top-k streams the matrix once more.
+        term_ops: one TermOps or None per query; a row with operands
+        selects among the documents that hold every required and no
+        excluded term, and masks the batch like a filter does."""
         import time as _time
         from ..ops import kernels as K
         if mark is None:
@@ -763,7 +826,8 @@ class GpuShard:
         N = self.n_docs
         k = min(k, N)
         topk = self._get_topk()
-        mask = _mask if _mask is not None else self._mask_for(filters, B)
+        mask = _mask if _mask is not None else self._mask_for(filters, B,
+                                                              term_ops)
         tp = _time.perf_counter()
         if scores_buf is not None and scores_buf.shape == (B, N):
             scores = scores_buf
@@ -826,14 +890,18 @@ class GpuShard:
                query_emb: torch.Tensor | None, k: int = 100,
                scores_buf: torch.Tensor | None = None,
                phase_t: dict | None = None,
-               filters: list[DocFilter | None] | None = None
+               filters: list[DocFilter | None] | None = None,
+               term_ops: list[TermOps | None] | None = None
                ) -> ShardHits:
         """Score all queries against this shard; returns fixed-size
         top-k with global ids (the per-peer result cap analogue,
         reference p2p/routing.py:48). filters: one DocFilter or None per
         query; filtered-out and deleted documents are never returned,
         and a row with fewer than k passing documents pads with
-        -inf / id -1."""
+        -inf / id -1. term_ops: one TermOps or None per query; both
+        planes return only documents that hold every required and no
+        excluded term (a required id that is nowhere in the shard
+        leaves the row all padding)."""
         import time as _time
 
         def mark(name, t0):
@@ -850,7 +918,7 @@ class GpuShard:
         assert N > 0, "shard is empty"
         k = min(k, N)
         tp = _time.perf_counter()
-        mask = self._mask_for(filters, B)   # once for both planes
+        mask = self._mask_for(filters, B, term_ops)   # once for both planes
         bm_vals, bm_idx = self.search_bm25(queries_terms, k,
                                            scores_buf=scores_buf,
                                            mark=mark, _mask=mask)
@@ -870,10 +938,10 @@ class GpuShard:
                          dense_ids=self.to_global(dn_idx))
 
     def search_dense(self, query_emb: torch.Tensor, k: int,
-                     mark=None, filters=None, _mask=None
+                     mark=None, filters=None, _mask=None, term_ops=None
                      ) -> tuple[torch.Tensor, torch.Tensor]:
         """Dense (cosine) plane; runs after the query embedding exists.
-        filters: as in search_bm25."""
+        filters, term_ops: as in search_bm25."""
         import time as _time
         from ..ops import kernels as K
         if mark is None:
@@ -882,7 +950,8 @@ class GpuShard:
         B = query_emb.shape[0]
         N = self.n_docs
         k = min(k, N)
-        mask = _mask if _mask is not None else self._mask_for(filters, B)
+        mask = _mask if _mask is not None else self._mask_for(filters, B,
+                                                              term_ops)
         tp = _time.perf_counter()
         emb = self.embeddings
         # hipGraph capture of the whole plane (GEMM + top-k passes, all
@@ -1003,21 +1072,41 @@ class CpuShard(GpuShard):
     def __init__(self, vocab: int = BM25_VOCAB, emb_dtype: str = "bf16"):
         super().__init__(device="cpu", vocab=vocab, emb_dtype=emb_dtype)
 
-    def _fail_rows(self, filters, B: int) -> torch.Tensor | None:
+    def _holds(self, term: int) -> np.ndarray:
+        """bool [N]: the documents with a posting for this term id."""
+        has = np.zeros(self.n_docs, dtype=bool)
+        for seg in self.segments:
+            b, e = int(seg.h_offs[term]), int(seg.h_offs[term + 1])
+            has[seg.doc_ids.numpy()[b:e].astype(np.int64) + seg.doc_base] = True
+        return has
+
+    def _fail_rows(self, filters, B: int,
+                   term_ops=None) -> torch.Tensor | None:
         """bool [B, N], True where a document fails its row's predicate
-        (the same packed words the GPU kernel reads); None when the
-        mask is inactive."""
+        (the same packed words the GPU kernel reads) or its row's term
+        operands (a required term it lacks, an excluded one it holds);
+        None when the mask is inactive."""
         pr = self._pred_rows(filters, B)
-        if pr is None:
+        trows = self._term_rows(term_ops, B)
+        if pr is None and not trows:
             return None
-        preds, rows, lists = pr
-        a = self.attrs.numpy()
-        if lists is None:
-            lists = [((), ())] * len(preds)
-        ok = np.stack([passes(a, p, allow=allow, block=block)
-                       for p, (allow, block) in zip(preds.view(np.uint32),
-                                                    lists)])
-        return torch.from_numpy(~ok[rows])
+        if pr is None:
+            fail = np.zeros((B, self.n_docs), dtype=bool)
+        else:
+            preds, rows, lists = pr
+            a = self.attrs.numpy()
+            if lists is None:
+                lists = [((), ())] * len(preds)
+            ok = np.stack([passes(a, p, allow=allow, block=block)
+                           for p, (allow, block) in zip(preds.view(np.uint32),
+                                                        lists)])
+            fail = ~ok[rows]
+        for i, t in trows:
+            for term in t.require:
+                fail[i] |= ~self._holds(term)
+            for term in t.exclude:
+                fail[i] |= self._holds(term)
+        return torch.from_numpy(fail)
 
     @staticmethod
     def _masked_topk(scores: torch.Tensor, fail: torch.Tensor | None,
@@ -1030,7 +1119,8 @@ class CpuShard(GpuShard):
                                  torch.full_like(idx, -1), idx)
 
     def search(self, queries_terms, query_emb, k: int = 100,
-               scores_buf=None, phase_t=None, filters=None) -> ShardHits:
+               scores_buf=None, phase_t=None, filters=None,
+               term_ops=None) -> ShardHits:
         B = len(queries_terms)
         N = self.n_docs
         assert N > 0, "shard is empty"
@@ -1054,7 +1144,7 @@ class CpuShard(GpuShard):
                     scores[qi, d] += (idf * tf * (BM25_K1 + 1)
                                       / (tf + norm[d]))
         st = torch.from_numpy(scores)
-        fail = self._fail_rows(filters, B)
+        fail = self._fail_rows(filters, B, term_ops)
         bm_vals, bm_idx = self._masked_topk(st, fail, k)
         if query_emb is not None and self.embeddings is not None:
             d_scores = query_emb.float().cpu() @ self.embeddings.float().T

@@ -241,15 +241,28 @@ class LocalStore:
                before: float | None = None,
                match_any: bool = False,
                include_domains=None,
-               exclude_domains=None) -> list[SearchHit]:
+               exclude_domains=None,
+               exclude_terms=()) -> list[SearchHit]:
         """FTS5 MATCH + bm25() ordering + snippet() with filters
         (reference: local_store.py:253-352). match_any=True ORs the
         terms (fact-check / recall-first queries). include_domains /
         exclude_domains: the stored domain must be IN / NOT IN the
-        list, compared exactly (lower-cased)."""
+        list, compared exactly (lower-cased). exclude_terms: words no
+        hit may hold, as `NOT "word"` after the query's own terms (the
+        reference's users write NOT into MATCH themselves); a query
+        left with no positive term returns nothing, since FTS5 has no
+        unary NOT. Required words need nothing here: the terms of a
+        MATCH are ANDed already."""
         fts_query = sanitize_fts_query(query, match_any=match_any)
         if not fts_query:
             return []
+        for word in exclude_terms or ():
+            banned = sanitize_fts_query(word)
+            if banned:
+                # one quoted phrase per word, whatever it tokenises to
+                banned = '"' + banned.replace('"', "") + '"'
+                fts_query = (f"({fts_query}) NOT {banned}" if match_any
+                             else f"{fts_query} NOT {banned}")
         sql = [
             "SELECT d.id, d.url, d.title, d.language, d.domain, d.crawled_at,",
             " bm25(documents_fts, 2.0, 1.0) AS rank,",

@@ -48,6 +48,10 @@ _SIGNATURES: dict[str, list] = {
                                 c_int, c_void_p],
     "infomesh_filter_bitmask_sets": [c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_long, c_int, c_void_p],
+    "infomesh_term_bitmask": [c_void_p, c_long, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_int, c_void_p, c_int,
+                              c_long, c_long, c_long, c_long, c_void_p],
+    "infomesh_term_block_docs": [],
     "infomesh_topk_workspace_u32": [c_int],
     "infomesh_topk_zero_u32": [c_int],
     "infomesh_bm25_block": [c_void_p, c_void_p, c_void_p, c_void_p,
@@ -110,11 +114,13 @@ _SIGNATURES: dict[str, list] = {
 
 # Everything not listed here returns void. topk_*_u32: lengths;
 # dense_scores, gemm_bf16_nt_bmax: dispatch eligibility (0 = launched);
-# gemm_tile: tile code; gemm_bmax_width: columns per block maximum.
+# gemm_tile: tile code; gemm_bmax_width: columns per block maximum;
+# term_block_docs: documents per workgroup of term_bitmask.
 _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
              "infomesh_topk_zero_u32": c_long,
              "infomesh_topk_pruned_workspace_u32": c_long,
              "infomesh_topk_pruned_zero_u32": c_long,
+             "infomesh_term_block_docs": c_int,
              "infomesh_gemm_bmax_width": c_int,
              "infomesh_gemm_bf16_nt_bmax": c_int,
              "infomesh_dense_scores": c_int,

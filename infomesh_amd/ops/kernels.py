@@ -466,6 +466,103 @@ def filter_bitmask_sets(attrs: torch.Tensor, preds: torch.Tensor,
     return bits
 
 
+TERM_OPS_MAX = 16   # operands per term row (csrc/termmask.hip)
+
+
+def term_block_docs() -> int:
+    """Documents per workgroup of term_bitmask (TERM_BLOCK)."""
+    return int(_ext.lib().infomesh_term_block_docs())
+
+
+def _host_i64(t: torch.Tensor, name: str, n: int) -> torch.Tensor:
+    assert t.dtype == torch.int64 and t.shape == (n,) and t.is_contiguous(), \
+        f"{name}: contiguous [{n}] i64"
+    return t.cpu()
+
+
+def term_bitmask(base_bits: torch.Tensor, src_row: torch.Tensor,
+                 segments, op_off: torch.Tensor, op_kind: torch.Tensor,
+                 N: int) -> torch.Tensor:
+    """Required / excluded terms -> pass bits (csrc/termmask.hip, where
+    the layout is written down). Term row r starts from
+    base_bits[src_row[r]] ([P, W] i32, W = ceil(N/64)*2, as
+    filter_bitmask writes them) and keeps document d's bit iff every
+    require operand of the row has a posting for d and no exclude
+    operand has one. Returns out [R, W] i32; base_bits is not written.
+
+    op_off [R+1] i32: per-row CSR into the operand arrays, at most
+    TERM_OPS_MAX operands per row; op_kind [T] i32, 0 = require,
+    1 = exclude. segments: one (doc_ids, doc_base, nseg, op_begin,
+    op_end) per posting segment, in any order: doc_ids the segment's
+    i32 ids (segment-local, ascending per term), op_begin / op_end [T]
+    i64 each operand's posting range in it (begin == end: term absent).
+    The segments' document ranges must not overlap and lie inside
+    [0, N).
+
+    The table is checked here, on the host, before a kernel indexes with
+    it: hand op_off, op_kind, op_begin and op_end over as host tensors
+    (they are then uploaded, no sync) or as device tensors (copied back
+    to check). One launch per segment, in stream order."""
+    _check(base_bits, torch.int32, "base_bits")
+    dev = base_bits.device
+    W = (N + 63) // 64 * 2
+    assert N >= 1 and base_bits.dim() == 2 and base_bits.shape[1] == W, \
+        "base_bits: [P, ceil(N/64)*2]"
+    P = base_bits.shape[0]
+    assert src_row.dim() == 1 and src_row.dtype in (torch.int32, torch.int64)
+    R = src_row.numel()
+    assert 1 <= R <= 0x7FFFFFFF
+    h_src = src_row.cpu().long()
+    assert bool((h_src >= 0).all()) and bool((h_src < P).all()), \
+        "src_row points outside base_bits"
+    assert op_off.dtype == torch.int32 and op_off.shape == (R + 1,) \
+        and op_off.is_contiguous(), "op_off: contiguous [R+1] i32"
+    assert op_kind.dtype == torch.int32 and op_kind.dim() == 1 \
+        and op_kind.is_contiguous(), "op_kind: contiguous [T] i32"
+    T = op_kind.numel()
+    h_off = op_off.cpu().long()
+    n_ops = h_off.diff()
+    assert int(h_off[0]) == 0 and bool((n_ops >= 0).all()) \
+        and int(h_off[-1]) == T, "op_off: ascending CSR over the T operands"
+    assert int(n_ops.max()) <= TERM_OPS_MAX, \
+        f"more than {TERM_OPS_MAX} operands in one row"
+    h_kind = op_kind.cpu()
+    assert bool(((h_kind == 0) | (h_kind == 1)).all()), "op_kind: 0 or 1"
+    spans = []
+    for doc_ids, doc_base, nseg, op_begin, op_end in segments:
+        _check(doc_ids, torch.int32, "doc_ids")
+        assert doc_ids.dim() == 1
+        hb = _host_i64(op_begin, "op_begin", T)
+        he = _host_i64(op_end, "op_end", T)
+        assert bool((hb >= 0).all()) and bool((hb <= he).all()) \
+            and bool((he <= doc_ids.numel()).all()), \
+            "operand range outside doc_ids"
+        assert 0 <= doc_base and nseg >= 0 and doc_base + nseg <= N, \
+            "segment outside [0, N)"
+        if nseg:
+            spans.append((int(doc_base), int(doc_base + nseg)))
+    spans.sort()
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), \
+        "segments overlap"
+    out = base_bits.index_select(0, src_row.to(dev).long())
+    if T == 0:
+        return out
+    off_d = op_off.to(dev, non_blocking=True)
+    kind_d = op_kind.to(dev, non_blocking=True)
+    lib = _ext.lib()
+    for doc_ids, doc_base, nseg, op_begin, op_end in segments:
+        if nseg == 0:
+            continue
+        b_d = op_begin.to(dev, non_blocking=True)
+        e_d = op_end.to(dev, non_blocking=True)
+        lib.infomesh_term_bitmask(
+            doc_ids.data_ptr(), doc_ids.numel(), off_d.data_ptr(),
+            b_d.data_ptr(), e_d.data_ptr(), kind_d.data_ptr(), T,
+            out.data_ptr(), R, W, N, int(doc_base), int(nseg),
+            _ext.stream_ptr())
+    return out
+
+
 def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
                qt_off: torch.Tensor, qt_ut: torch.Tensor,
                qt_idf: torch.Tensor, u_begin: torch.Tensor,

@@ -187,6 +187,39 @@ def filter_bitmask_sets(attrs: torch.Tensor, preds: torch.Tensor,
     return torch.from_numpy(np.stack(rows).view(np.int32).reshape(-1, W))
 
 
+def term_bitmask(base_bits: torch.Tensor, src_row: torch.Tensor,
+                 segments, op_off: torch.Tensor, op_kind: torch.Tensor,
+                 N: int) -> torch.Tensor:
+    """Oracle of csrc/termmask.hip, same signature as
+    kernels.term_bitmask: plain set arithmetic over the posting arrays.
+    Row r starts from base_bits[src_row[r]]; inside every segment's
+    document range a document keeps its bit iff it is in the posting
+    set of every require operand (kind 0) and of no exclude operand
+    (kind 1). Documents outside every segment keep their base bit."""
+    import numpy as np
+    W = (N + 63) // 64 * 2
+    words = base_bits.cpu().numpy().view(np.uint32)
+    base_ok = np.unpackbits(words.view(np.uint8), axis=1,
+                            bitorder="little").astype(bool)     # [P, W*32]
+    off = op_off.cpu().numpy().astype(np.int64)
+    kind = op_kind.cpu().numpy()
+    rows = []
+    for r, p in enumerate(src_row.cpu().numpy().astype(np.int64)):
+        ok = base_ok[p].copy()
+        for doc_ids, doc_base, nseg, op_begin, op_end in segments:
+            ids = doc_ids.cpu().numpy().astype(np.int64)
+            begin = op_begin.cpu().numpy()
+            end = op_end.cpu().numpy()
+            in_seg = np.arange(doc_base, doc_base + nseg)
+            keep = np.ones(nseg, dtype=bool)
+            for t in range(off[r], off[r + 1]):
+                has = np.isin(in_seg, ids[begin[t]:end[t]] + doc_base)
+                keep &= ~has if kind[t] else has
+            ok[doc_base:doc_base + nseg] &= keep
+        rows.append(np.packbits(ok, bitorder="little").view(np.uint32))
+    return torch.from_numpy(np.stack(rows).view(np.int32).reshape(-1, W))
+
+
 def masked_topk(scores: torch.Tensor, k: int, bits: torch.Tensor,
                 row_pred: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Oracle of the masked top-k: failing columns become -inf, then

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from ..index.doc_attrs import (HAS_ALLOW_BIT, HAS_BLOCK_BIT, U32_MAX,
-                               pack_pred_sets)
+                               TermOps, pack_pred_sets)
 from ..index.gpu_index import GpuShard, ShardHits
 from .fabric import Fabric
 
@@ -34,6 +34,55 @@ MAX_QUERY_TERMS = 32
 _PRED_COLS = 2
 _HAS_FILTER = 1 << 17
 _HAS_LISTS = HAS_ALLOW_BIT | HAS_BLOCK_BIT
+# Term operands (TermOps) ride in the same broadcast, as flag bits on the
+# row's term entries; term ids are below 2^17, so bits 40.. are free. A
+# require operand is its scoring term with bit 40 set, an exclude operand
+# an extra entry with bit 41 set, which is no scoring term. A require id
+# that is not among the row's scoring terms carries bit 42 as well and is
+# not scored either. Operands come first in the row, so the cut at
+# MAX_QUERY_TERMS entries drops scoring terms, never an operand.
+_OP_REQUIRE = 1 << 40
+_OP_EXCLUDE = 1 << 41
+_OP_UNSCORED = 1 << 42
+_OP_FLAGS = _OP_REQUIRE | _OP_EXCLUDE | _OP_UNSCORED
+
+
+def pack_term_row(terms: np.ndarray, ops: TermOps | None,
+                  T: int = MAX_QUERY_TERMS) -> np.ndarray:
+    """One query's entries of the terms broadcast, at most T: the
+    operands, flagged, then the remaining scoring terms. A required id
+    stands for ONE of its occurrences among the scoring terms; repeats
+    stay behind it, so the receivers see every term as often as rank 0
+    does. The order differs from the caller's; the shards dedupe and
+    sort a row's terms before scoring (GpuShard.dedupe_terms), so
+    neither order nor repeats change a score."""
+    terms = np.asarray(terms, dtype=np.int64)
+    if not ops:
+        return terms[:T]
+    rest = terms.tolist()
+    head = []
+    for t in ops.require:
+        if t in rest:
+            rest.remove(t)              # the first occurrence only
+            head.append(t | _OP_REQUIRE)
+        else:
+            head.append(t | _OP_REQUIRE | _OP_UNSCORED)
+    head += [t | _OP_EXCLUDE for t in ops.exclude]
+    return np.asarray(head + rest, dtype=np.int64)[:T]
+
+
+def unpack_term_row(row: np.ndarray) -> tuple[np.ndarray, TermOps | None]:
+    """(scoring terms, TermOps or None) of a row pack_term_row wrote
+    (negative entries are padding)."""
+    row = np.asarray(row, dtype=np.int64)
+    row = row[row >= 0]
+    ids = row & ~np.int64(_OP_FLAGS)
+    unscored = (row & np.int64(_OP_EXCLUDE | _OP_UNSCORED)) != 0
+    req = ids[(row & np.int64(_OP_REQUIRE)) != 0]
+    exc = ids[(row & np.int64(_OP_EXCLUDE)) != 0]
+    ops = TermOps.of(req.tolist(), exc.tolist()) \
+        if len(req) or len(exc) else None
+    return ids[~unscored], ops
 
 
 @dataclass
@@ -136,9 +185,11 @@ class DistributedQueryPlane:
                      phase_t: dict | None = None,
                      encode_fn=None,
                      encode_shard=None,
-                     filters: list | None = None) -> FusedHits | None:
+                     filters: list | None = None,
+                     term_ops: list | None = None) -> FusedHits | None:
         """filters (rank 0): one DocFilter or None per row; every shard
-        applies them in its top-k selection.
+        applies them in its top-k selection. term_ops (rank 0): one
+        TermOps or None per row, honoured by every shard alike.
 
         Collective search with rank-fault tolerance: on a collective
         failure (dead rank → timeout) the fabric shrinks to the
@@ -148,7 +199,8 @@ class DistributedQueryPlane:
         try:
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
-                                      encode_fn, encode_shard, filters)
+                                      encode_fn, encode_shard, filters,
+                                      term_ops)
         except RuntimeError as e:
             if not self.fabric.initialized or not self.fabric.collective_ok:
                 raise
@@ -181,7 +233,8 @@ class DistributedQueryPlane:
                     if r != self.fabric.rank))
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
-                                      encode_fn, encode_shard, filters)
+                                      encode_fn, encode_shard, filters,
+                                      term_ops)
 
     def _sharded_encode(self, encode_shard: dict, B: int,
                         dim: int) -> torch.Tensor:
@@ -220,8 +273,8 @@ class DistributedQueryPlane:
                       B: int, dim: int = 384, n_results: int = 10,
                       use_dense: bool = True,
                       phase_t: dict | None = None,
-                      encode_fn=None, encode_shard=None, filters=None
-                      ) -> FusedHits | None:
+                      encode_fn=None, encode_shard=None, filters=None,
+                      term_ops=None) -> FusedHits | None:
         """One collective search attempt. Rank 0 passes real queries and
         gets the FusedHits; other ranks pass None and get None.
 
@@ -247,11 +300,12 @@ class DistributedQueryPlane:
                                            encode_fn, B, dim, use_dense,
                                            phase_t=phase_t,
                                            encode_shard=encode_shard,
-                                           filters=filters)
+                                           filters=filters,
+                                           term_ops=term_ops)
             tp = mark("plane.shard", tp)
         else:
-            terms, filters = self._broadcast_terms(queries_terms, B,
-                                                   filters)
+            terms, filters, term_ops = self._broadcast_query(
+                queries_terms, B, filters, term_ops)
             if encode_shard is not None:
                 emb = self._sharded_encode(encode_shard, B, dim).float()
             else:
@@ -266,7 +320,7 @@ class DistributedQueryPlane:
             hits = self.shard.search(
                 terms, emb if use_dense else None, k=self.k,
                 scores_buf=self._get_scores_buf(B), phase_t=phase_t,
-                filters=filters)
+                filters=filters, term_ops=term_ops)
             tp = mark("plane.shard", tp)
         # ONE packed all-gather instead of four: xGMI collectives at
         # this payload size (a few hundred KB) are latency-dominated,
@@ -323,7 +377,8 @@ class DistributedQueryPlane:
 
     def _search_overlapped(self, queries_terms, query_emb, encode_fn,
                            B, dim, use_dense, phase_t=None,
-                           encode_shard=None, filters=None) -> ShardHits:
+                           encode_shard=None, filters=None,
+                           term_ops=None) -> ShardHits:
         """BM25 on a side stream || query encoding on the main stream.
 
         Broadcast order (terms, then embeddings) is identical on all
@@ -346,14 +401,22 @@ class DistributedQueryPlane:
             self._bm25_stream = torch.cuda.Stream(dev)
         # terms must be broadcast before any rank's shard work
         tp = _time.perf_counter()
-        terms, filters = self._broadcast_terms(queries_terms, B, filters)
+        terms, filters, term_ops = self._broadcast_query(
+            queries_terms, B, filters, term_ops)
         tp = mark("ov.terms", tp)
         main = torch.cuda.current_stream(dev)
+        mask = None
+        if term_ops is not None:
+            # the operand kernel walks posting lists: run it once, here,
+            # for both planes (the side stream below waits for this one)
+            mask = self.shard._mask_for(filters, B, term_ops)
+            for t in mask or ():
+                t.record_stream(self._bm25_stream)
         self._bm25_stream.wait_stream(main)
         with torch.cuda.stream(self._bm25_stream):
             bm_vals, bm_idx = self.shard.search_bm25(
                 terms, self.k, scores_buf=self._get_scores_buf(B),
-                filters=filters)
+                filters=filters, _mask=mask)
             bm_ids = self.shard.to_global(bm_idx)
         tp = mark("ov.bm25", tp)
         if encode_shard is not None:
@@ -369,7 +432,8 @@ class DistributedQueryPlane:
         tp = mark("ov.encode", tp)
         if use_dense and self.shard.embeddings is not None:
             dn_vals, dn_idx = self.shard.search_dense(emb_t, self.k,
-                                                      filters=filters)
+                                                      filters=filters,
+                                                      _mask=mask)
             dn_ids = self.shard.to_global(dn_idx)
             tp = mark("ov.dense", tp)
         else:
@@ -381,13 +445,23 @@ class DistributedQueryPlane:
                          dense_scores=dn_vals, dense_ids=dn_ids)
 
     def _broadcast_terms(self, queries_terms, B, filters=None):
-        """-> (terms, filters) as every rank must see them. At world > 1
-        the predicates ride in the one terms broadcast (packed words,
-        which the shards accept in place of DocFilter objects)."""
+        """-> (terms, filters) of a batch without term operands."""
+        return self._broadcast_query(queries_terms, B, filters)[:2]
+
+    def _broadcast_query(self, queries_terms, B, filters=None,
+                         term_ops=None):
+        """-> (terms, filters, term_ops) as every rank must see them. At
+        world > 1 the predicates ride in the one terms broadcast (packed
+        words, which the shards accept in place of DocFilter objects),
+        and so do the term operands, as flag bits on the term entries
+        (pack_term_row). term_ops comes back None when no row has an
+        operand."""
+        if term_ops is not None and not any(term_ops):
+            term_ops = None
         if self.fabric.world == 1 and queries_terms is not None:
             # no collective needed: skip the pack + GPU round-trip +
             # device sync entirely
-            return queries_terms, filters
+            return queries_terms, filters, term_ops
         dev = self.fabric.device
         T = MAX_QUERY_TERMS
         terms_t = torch.full((B, T + _PRED_COLS), -1, dtype=torch.int64)
@@ -395,7 +469,7 @@ class DistributedQueryPlane:
         lists: dict = {}      # row -> (allow, block), rank 0 only
         if queries_terms is not None:
             for i, t in enumerate(queries_terms):
-                t = t[:T]
+                t = pack_term_row(t, term_ops[i] if term_ops else None, T)
                 terms_t[i, :len(t)] = torch.from_numpy(t.astype(np.int64))
             if filters is not None:
                 cols = np.zeros((B, _PRED_COLS), dtype=np.uint64)
@@ -423,7 +497,10 @@ class DistributedQueryPlane:
                 # every rank read the same flag bits, so all of them
                 # take this branch together
                 self._broadcast_lists(filters, lists, B)
-        return [tt[i, :T][tt[i, :T] >= 0] for i in range(B)], filters
+        rows = [unpack_term_row(tt[i, :T]) for i in range(B)]
+        term_ops = [ops for _, ops in rows]
+        return ([terms for terms, _ in rows], filters,
+                term_ops if any(term_ops) else None)
 
     def _broadcast_lists(self, filters: list, lists: dict, B: int) -> None:
         """The domain lists of a batch whose flag bits announce some:

@@ -189,6 +189,42 @@ def parse_query_filters(query: str) -> ParsedQuery:
     return pq
 
 
+# +word / -word: the sign counts only at the start of a token and
+# directly before a word character; the token runs to the next white
+# space. A token with a colon (-site:a.org, +lang:de) is filter syntax
+# and is left alone.
+_TERM_OP_RE = re.compile(r"(?<!\S)([+-])(\w[^\s:]*)(?!\S)")
+
+
+def is_term_operator(token: str) -> bool:
+    """Is this white-space-delimited token a +word / -word operator?"""
+    return _TERM_OP_RE.fullmatch(token) is not None
+
+
+def parse_term_operators(text: str
+                         ) -> tuple[str, tuple[str, ...], tuple[str, ...]]:
+    """Split the +word / -word operators off a query (applied to the
+    text parse_query_filters leaves) -> (text, require_words,
+    exclude_words). A required word stays in the text without its plus,
+    so it is still scored; an excluded word leaves the text. A bare
+    "-", a hyphen inside a word ("well-known") and "-site:" are not
+    operators and stay as they are. Words come back lower-cased, without
+    repeats, in order of appearance."""
+    require: list[str] = []
+    exclude: list[str] = []
+
+    def _sub(m: re.Match) -> str:
+        sign, word = m.group(1), m.group(2)
+        (require if sign == "+" else exclude).append(word.lower())
+        return word if sign == "+" else ""
+    out = _TERM_OP_RE.sub(_sub, text)
+    if not require and not exclude:
+        return text, (), ()
+    out = re.sub(r"\s{2,}", " ", out).strip()
+    return (out, tuple(dict.fromkeys(require)),
+            tuple(dict.fromkeys(exclude)))
+
+
 def _site_names(val: str) -> tuple[str, ...]:
     """The lower-cased names of a comma-separated site value, in order,
     without repeats. Lists match the stored domain exactly, so a

@@ -19,7 +19,8 @@ from ..index.local_store import LocalStore, SearchHit
 from ..index.ranking import rank_local_results, AuthorityFn, TrustFn
 from .cjk import tokenize_query_cjk
 from .merge import MergedHit, merge_results
-from .nlp import expand_query, parse_query_filters, remove_stop_words
+from .nlp import (expand_query, is_term_operator, parse_query_filters,
+                  parse_term_operators, remove_stop_words)
 from .passage import select_best_passage, highlight
 
 
@@ -50,24 +51,45 @@ class SearchResponse:
     total_candidates: int = 0
 
 
-def preprocess_query(query: str, language: str = "en") -> str:
+def preprocess_query(query: str, language: str = "en",
+                     term_operators: bool = False) -> str:
+    """term_operators: +word / -word tokens are set aside first and come
+    back verbatim at the end of the text, for parse_term_operators to
+    read: the CJK splitter would otherwise part the sign from its word
+    (`-東京都` -> `- 東京 京都`) and the stop-word filter could drop a
+    required word. The operator words are tokenised where they are
+    used, by bm25_term_ids, CJK bigrams included."""
+    ops: list[str] = []
+    if term_operators:
+        tokens = query.split()
+        ops = [t for t in tokens if is_term_operator(t)]
+        if ops:
+            query = " ".join(t for t in tokens if not is_term_operator(t))
     q = tokenize_query_cjk(query.strip())
     q = remove_stop_words(q, language)
-    return q
+    return " ".join([q, *ops]).strip() if ops else q
 
 
 def search_local(store: LocalStore, query: str, limit: int = 10,
                  authority_fn: AuthorityFn | None = None,
                  boost_fn=None,
                  trust_fn: TrustFn | None = None,
-                 enhance_snippets: bool = True) -> SearchResponse:
+                 enhance_snippets: bool = True,
+                 term_operators: bool = False) -> SearchResponse:
+    """term_operators (config gpu.term_operators): read +word / -word
+    in the query; excluded words go to the store as NOT terms, required
+    ones stay in the text, which FTS5 ANDs anyway."""
     t0 = time.perf_counter()
     pq = parse_query_filters(query)
-    eff = preprocess_query(pq.text)
+    text, banned = pq.text, ()
+    if term_operators:
+        text, _, banned = parse_term_operators(text)
+    eff = preprocess_query(text)
     hits = store.search(eff, limit=limit * 2, language=pq.language,
                         domain=pq.site, after=pq.after, before=pq.before,
                         include_domains=pq.sites,
-                        exclude_domains=pq.exclude_sites)
+                        exclude_domains=pq.exclude_sites,
+                        exclude_terms=banned)
     expanded: list[str] = []
     if len(hits) < max(3, limit // 2):
         # Sparse results → synonym expansion (query.py:136-156).
@@ -76,7 +98,8 @@ def search_local(store: LocalStore, query: str, limit: int = 10,
             more = store.search(alt, limit=limit, language=pq.language,
                                 domain=pq.site, after=pq.after, before=pq.before,
                                 include_domains=pq.sites,
-                                exclude_domains=pq.exclude_sites)
+                                exclude_domains=pq.exclude_sites,
+                                exclude_terms=banned)
             seen = {h.url for h in hits}
             hits.extend(h for h in more if h.url not in seen)
             if len(hits) >= limit:
@@ -100,11 +123,13 @@ def search_hybrid(store: LocalStore, dense: DenseSearcher | None,
                   query: str, limit: int = 10,
                   authority_fn: AuthorityFn | None = None,
                   trust_fn: TrustFn | None = None,
-                  rrf_k: int = 60, boost_fn=None) -> SearchResponse:
+                  rrf_k: int = 60, boost_fn=None,
+                  term_operators: bool = False) -> SearchResponse:
     t0 = time.perf_counter()
     local = search_local(store, query, limit=limit * 2,
                          authority_fn=authority_fn, trust_fn=trust_fn,
-                         enhance_snippets=False, boost_fn=boost_fn)
+                         enhance_snippets=False, boost_fn=boost_fn,
+                         term_operators=term_operators)
     lists: list[Sequence[SearchHit]] = [local.results]
     sources = ["fts"]
     weights = [1.0]

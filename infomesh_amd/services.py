@@ -24,12 +24,13 @@ from .crawler.worker import CrawlResult, CrawlWorker
 from .engine import HybridEngine
 from .errors import GpuExtensionMissing, InfoMeshError
 from .index.doc_attrs import DocFilter, pack_pred_sets
+from .index.gpu_index import bm25_term_ids
 from .index.link_graph import LinkGraph
 from .index.local_store import Document, LocalStore
 from .search.batcher import QueryBatcher
 from .search.cache import QueryCache
 from .search.nlp import (RelatedSearchTracker, parse_query_filters,
-                         with_filter_tokens)
+                         parse_term_operators, with_filter_tokens)
 from .search.passage import fast_snippet
 from .search.query import (SearchResponse, preprocess_query,
                            search_hybrid, search_local)
@@ -40,6 +41,11 @@ from .trust.keys import KeyPair, ensure_keys
 from .trust.scoring import TrustStore
 
 log = logging.getLogger("infomesh.services")
+
+# The shards hash words into 2^17 term ids; the hydration guard for
+# required words compares the same tokens hashed into 2^62, where two
+# words do not meet in practice.
+_GUARD_VOCAB = 1 << 62
 
 
 @dataclass
@@ -314,11 +320,13 @@ class AppContext:
                 # batch inside the batcher's executor
                 pack_pred_sets(DocFilter(sites=pq.sites,
                                          exclude_sites=pq.exclude_sites))
+        term_operators = self.config.gpu.term_operators
         if mode == "local" or (mode == "auto" and not engine_ready):
             resp = search_local(self.store, query, limit=limit,
                                 authority_fn=authority, trust_fn=trust_fn,
                                 boost_fn=(self.feedback.url_boost
-                                          if self.feedback else None))
+                                          if self.feedback else None),
+                                term_operators=term_operators)
         elif mode in ("auto", "hybrid", "distributed"):
             if engine_ready and not has_filters:
                 # single-fusion path: the GPU plane RRF-fuses BM25 +
@@ -331,7 +339,8 @@ class AppContext:
                     authority_fn=authority, trust_fn=trust_fn,
                     rrf_k=self.config.search.rrf_k,
                     boost_fn=(self.feedback.url_boost
-                              if self.feedback else None))
+                              if self.feedback else None),
+                    term_operators=term_operators)
                 if mode == "distributed":
                     resp.mode = "distributed"
         else:
@@ -375,7 +384,13 @@ class AppContext:
         dropped when its stored domain contradicts them. For site: that
         is a curiosity; for a 2048-entry list against ~1M distinct
         domains it is an expected event (2048 * 1M / 2^32 ~ 0.5 false
-        matches per query), so the guard covers the lists too."""
+        matches per query), so the guard covers the lists too.
+
+        With gpu.term_operators the +word / -word operators are split
+        off the text here as well and go to the engine as require /
+        exclude words. Term ids are buckets of a 2^17-entry hash, so a
+        hit that passed a required word is re-checked against the
+        stored text."""
         if self.batcher is not None \
                 and self.batcher.engine is not self.engine:
             self.batcher.engine = self.engine   # engine was rebound
@@ -394,13 +409,30 @@ class AppContext:
                     or pq.sites or pq.exclude_sites)
                 else None for pq in parsed]
             queries = [pq.text for pq in parsed]
-        per_q = self.engine.search_many(queries, limit=limit,
-                                        filters=filters)
+        required: list = [None] * len(queries)
+        if self.config.gpu.term_operators:
+            # +word / -word travel in the text as well: a required word
+            # stays in it, an excluded one leaves it
+            split = [parse_term_operators(q) for q in queries]
+            queries = [text for text, _, _ in split]
+            required = [
+                {int(i) for w in req
+                 for i in bm25_term_ids(w, vocab=_GUARD_VOCAB)} or None
+                for _, req, _ in split]
+            per_q = self.engine.search_many(
+                queries, limit=limit, filters=filters,
+                require=[req for _, req, _ in split],
+                exclude=[exc for _, _, exc in split])
+        else:
+            per_q = self.engine.search_many(queries, limit=limit,
+                                            filters=filters)
         gids = [h.doc_id for hits in per_q for h in hits]
         docs = self.store.get_documents(gids)
         out: list[list] = []
-        for q, hits, pq in zip(queries, per_q, parsed):
+        for q, hits, pq, req in zip(queries, per_q, parsed, required):
             hydrated = []
+            if self.config.gpu.term_operators and not q.strip():
+                hits = []    # only exclusions: nothing to rank, as on FTS
             for h in hits:
                 doc = docs.get(h.doc_id)
                 if doc is None:
@@ -410,6 +442,15 @@ class AppContext:
                         or (pq.sites and doc.domain not in pq.sites)
                         or doc.domain in pq.exclude_sites):
                     continue   # 32-bit domain-hash collision guard
+                if req is not None and doc.text and not req <= set(
+                        bm25_term_ids(f"{doc.title}\n{doc.text}"[:4000],
+                                      vocab=_GUARD_VOCAB).tolist()):
+                    # (the text as HybridEngine.add_document cuts it)
+                    # 2^17-bucket term-hash collision guard: the shard
+                    # passed a document that holds only a word colliding
+                    # with a required one. (An excluded word can only
+                    # over-exclude, which no guard here can undo.)
+                    continue
                 h.url, h.title = doc.url, doc.title
                 h.domain, h.crawled_at = doc.domain, doc.crawled_at
                 if doc.text:
@@ -435,7 +476,17 @@ class AppContext:
         if self.otlp is not None and self.otlp.enabled:
             from .utils.observability import QueryTrace
             trace = QueryTrace(query)
-        eff = preprocess_query(query)
+        term_operators = self.config.gpu.term_operators
+        # +word / -word tokens pass through verbatim, behind the text
+        eff = preprocess_query(query, term_operators=term_operators)
+        if term_operators:
+            # over the operand cap: fail this caller here, not the whole
+            # batch inside the batcher's executor; on the text as
+            # _batch_execute will see it. Only the engine has a cap.
+            text = eff
+            if self.config.gpu.filters:
+                text = parse_query_filters(text).text
+            self.engine.term_ops_for(*parse_term_operators(text))
         batcher = self.ensure_batcher()
         if trace is not None:
             with trace.span("engine"):
