@@ -75,22 +75,34 @@ def create_app(ctx: AppContext, api_key: str = "",
     @app.get("/search")
     def search(q: str, limit: int = 10, mode: str = "auto",
                include_domains: str = "", exclude_domains: str = "",
-               recency_days: float = 0):
+               recency_days: float = 0, facets: int = 0,
+               facet_domains: str = ""):
         """include_domains / exclude_domains: comma-separated exact
-        domains to allow / block; recency_days: crawled that recently."""
+        domains to allow / block; recency_days: crawled that recently.
+        facets=1 adds "total_matches" and "facets" to the answer
+        (AppContext.search says what they cover); facet_domains:
+        comma-separated domains to count."""
         if not q.strip():
             raise HTTPException(400, "empty query")
+        kw = {}
+        if facets:
+            kw = {"facets": True,
+                  "facet_domains": [d for d in facet_domains.split(",") if d]}
         try:
             resp = ctx.search(
                 q, limit=min(limit, 50), mode=mode,
                 include_domains=[d for d in include_domains.split(",") if d],
                 exclude_domains=[d for d in exclude_domains.split(",") if d],
-                recency_days=recency_days)
+                recency_days=recency_days, **kw)
         except ValueError as e:      # domain lists over the cap
             raise HTTPException(400, str(e)) from e
-        return {"query": q, "mode": resp.mode,
-                "elapsed_ms": round(resp.elapsed_ms, 2),
-                "results": [result_to_dict(r) for r in resp.results]}
+        out = {"query": q, "mode": resp.mode,
+               "elapsed_ms": round(resp.elapsed_ms, 2),
+               "results": [result_to_dict(r) for r in resp.results]}
+        if facets:
+            out["total_matches"] = resp.total_matches
+            out["facets"] = resp.facets
+        return out
 
     @app.get("/status")
     def status():

@@ -25,6 +25,12 @@ _MARKERS: dict[str, frozenset[str]] = {
 _WORD_RE = re.compile(r"[a-zà-ÿäöüßñç]+", re.I)
 
 
+def known_languages() -> tuple[str, ...]:
+    """Every code detect_language can return, sorted (the language
+    facet lists exactly these)."""
+    return tuple(sorted({lang for lang, _ in _SCRIPTS} | set(_MARKERS)))
+
+
 def detect_language(text: str) -> str:
     """Best-effort ISO-639-1 code; '' when unknown."""
     if not text:

@@ -17,7 +17,8 @@ import time
 import numpy as np
 import torch
 
-from .index.doc_attrs import DocFilter, TermOps, pack_attrs
+from .index.doc_attrs import (DocFilter, FacetCounts, FacetSpec, TermOps,
+                              facet_results, pack_attrs, pack_facets)
 from .index.gpu_index import CpuShard, GpuShard, bm25_term_ids
 from .index.local_store import (Document, LocalStore, SearchHit,
                                 extract_domain)
@@ -235,9 +236,36 @@ class HybridEngine:
         selection. require / exclude: one tuple of words (or None) per
         query; a hit holds every required word and no excluded one, on
         both planes (term_ops_for says how words become operands)."""
+        return self._search_many(queries, limit, use_dense, filters,
+                                 require, exclude, None)[0]
+
+    def search_with_facets(self, queries: list[str], limit: int = 10,
+                           use_dense: bool | None = None,
+                           filters: list[DocFilter | None] | None = None,
+                           require: list[tuple[str, ...] | None] | None = None,
+                           exclude: list[tuple[str, ...] | None] | None = None,
+                           facets: FacetSpec | None = None
+                           ) -> tuple[list[list[SearchHit]],
+                                      list[FacetCounts | None]]:
+        """search_many plus, per query, the counts of a FacetSpec over
+        EVERY matching document of every shard, not over the returned
+        hits: (hits, one FacetCounts or None per query). A document
+        matches iff it passes the query's filter and operands, is not
+        deleted, and holds at least one query term (FacetSpec says it in
+        full). The hits are those of search_many; a query whose entry in
+        facets.domains is None (or missing) gets None."""
+        return self._search_many(queries, limit, use_dense, filters,
+                                 require, exclude, facets)
+
+    def _search_many(self, queries, limit, use_dense, filters, require,
+                     exclude, facets):
+        """The one body of search_many and search_with_facets ->
+        (hits per query, FacetCounts or None per query)."""
         if self.shard.n_docs == 0 or not queries:
-            return [[] for _ in queries]
+            return [[] for _ in queries], [None] * len(queries)
         B = len(queries)
+        if facets is not None and len(facets.domains) > B:
+            raise ValueError("facets: more domain lists than queries")
         term_ops = None
         if require is not None or exclude is not None:
             require = require or [None] * B
@@ -269,12 +297,18 @@ class HybridEngine:
                        if any(f is not None for f in filters) else None)
         if term_ops is not None:
             term_ops = term_ops + [None] * (Bp - B)
+        # padding rows are past the end of facets.domains: never counted
+        packed = pack_facets(facets, Bp)
         fused = self.plane.search_batch(
             terms, emb, B=Bp, dim=emb.shape[1] if emb is not None else 384,
             n_results=limit, use_dense=use_dense and emb is not None,
-            filters=filters, term_ops=term_ops)
+            filters=filters, term_ops=term_ops, facets=packed)
         if fused is None:
-            return [[] for _ in queries]
+            return [[] for _ in queries], [None] * B
+        counts: list[FacetCounts | None] = [None] * B
+        if fused.facets is not None:
+            counts = facet_results(facets, packed, fused.facets.cpu().numpy(),
+                                   n_rows=B)
         ids = fused.ids.tolist()
         scores = fused.scores.tolist()
         out: list[list[SearchHit]] = []
@@ -288,7 +322,7 @@ class HybridEngine:
                                       score=float(score),
                                       source="gpu-hybrid"))
             out.append(hits)
-        return out
+        return out, counts
 
     def stats(self) -> dict:
         return {

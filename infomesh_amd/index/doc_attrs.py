@@ -114,6 +114,185 @@ class TermOps:
         return bool(self.require or self.exclude)
 
 
+FACET_MAX_EDGES = 7     # date edges per batch      (ops/csrc/facets.hip)
+FACET_MAX_LANGS = 32    # listed languages per batch
+FACET_MAX_DOMS = 64     # domain hashes per row
+
+
+def facet_slots(E: int, L: int) -> dict[str, int]:
+    """First slot of every group of a facet count row for E date edges
+    and L listed languages; the layout is written down in the header of
+    ops/csrc/facets.hip, and the extension reports the same numbers
+    (ops/kernels.facet_slots)."""
+    return {"total": 0, "date_zero": 1, "date0": 2, "lang_zero": 3 + E,
+            "lang0": 4 + E, "lang_other": 4 + E + L, "dom0": 5 + E + L}
+
+
+def facet_width(E: int, L: int, Dw: int) -> int:
+    """Slots per count row: Dw is the widest domain list of the batch."""
+    return 5 + E + L + Dw
+
+
+@dataclass(frozen=True)
+class FacetSpec:
+    """What to count over a batch's match sets. A document matches a
+    row iff it passes the row's filter, domain lists and term operands,
+    is not deleted, and holds at least one of the row's query terms
+    (BM25 score > 0); the dense plane takes no part.
+
+    date_edges: u32 seconds, one list per batch; a document with
+    crawled_at != 0 falls into bucket #{edges <= floor(crawled_at)}.
+    languages: 2-letter codes, one list per batch. domains: one entry
+    per row, a tuple of domain names to count or None for a row that is
+    not counted. Domains count by their 32-bit hash (domain_hash), as
+    the filters compare them: two names with one hash share a count."""
+    date_edges: tuple[int, ...] = ()
+    languages: tuple[str, ...] = ()
+    domains: tuple[tuple[str, ...] | None, ...] = ()
+
+
+@dataclass(frozen=True)
+class FacetCounts:
+    """One row's counts, mapped back to the caller's FacetSpec.
+    dates[i]: documents with exactly i of the sorted, deduped edges
+    <= crawled_at (len(edges) + 1 buckets); date_zero: crawled_at == 0.
+    languages / domains: one count per name, in the caller's order.
+    total == date_zero + sum(dates) == language_zero + language_other
+    + (the counts of the distinct listed languages)."""
+    total: int
+    date_zero: int
+    dates: tuple[int, ...]
+    languages: dict
+    language_zero: int
+    language_other: int
+    domains: dict
+
+
+@dataclass(frozen=True)
+class PackedFacets:
+    """A FacetSpec as the kernel reads it (and as the query plane
+    forwards it between ranks): edges and language codes ascending and
+    unique, `rows` the counted batch rows, `lists` each one's domain
+    hashes, unique and ascending as unsigned."""
+    edges: tuple[int, ...]
+    langs: tuple[int, ...]
+    rows: tuple[int, ...]
+    lists: tuple[tuple[int, ...], ...]
+
+    def __post_init__(self):
+        widest = max((len(h) for h in self.lists), default=0)
+        if len(self.edges) > FACET_MAX_EDGES \
+                or len(self.langs) > FACET_MAX_LANGS \
+                or widest > FACET_MAX_DOMS:
+            raise ValueError(
+                f"facets: {len(self.edges)} date edges, {len(self.langs)} "
+                f"languages, {widest} domains in one row; the caps are "
+                f"{FACET_MAX_EDGES}, {FACET_MAX_LANGS} and {FACET_MAX_DOMS}")
+        assert len(self.rows) == len(self.lists)
+
+    @property
+    def width(self) -> int:
+        return facet_width(len(self.edges), len(self.langs),
+                           max((len(h) for h in self.lists), default=0))
+
+    def tables(self):
+        """(rows [R], edges [E], langs [L], dom_desc [R, 2], doms) as
+        int32 arrays with the u32 bits, for facet_counts."""
+        def u32(v):
+            return np.asarray(v, dtype=np.uint32).view(np.int32)
+        desc = np.zeros((len(self.rows), 2), dtype=np.int32)
+        flat: list[int] = []
+        for r, h in enumerate(self.lists):
+            desc[r] = (len(flat), len(h))
+            flat.extend(h)
+        return (np.asarray(self.rows, dtype=np.int32), u32(self.edges),
+                u32(self.langs), desc, u32(flat))
+
+
+def pack_facets(spec, B: int) -> PackedFacets | None:
+    """FacetSpec -> PackedFacets for a batch of B rows (spec.domains may
+    be shorter: the rows past its end are not counted); a PackedFacets
+    passes through. None when no row is counted. Over a cap, or a
+    language that is no 2-letter ASCII code, is a ValueError."""
+    if spec is None or isinstance(spec, PackedFacets):
+        return spec if spec is None or spec.rows else None
+    if len(spec.domains) > B:
+        raise ValueError("facets: more domain lists than rows")
+    codes = [lang16(c) for c in spec.languages]
+    if 0 in codes:
+        raise ValueError("facets: languages are 2-letter ASCII codes")
+    rows = tuple(i for i, d in enumerate(spec.domains) if d is not None)
+    if not rows:
+        return None
+    return PackedFacets(
+        edges=tuple(sorted({_clamp_u32(e) for e in spec.date_edges})),
+        langs=tuple(sorted(set(codes))), rows=rows,
+        lists=tuple(_hash_list(spec.domains[i]) for i in rows))
+
+
+def facet_results(spec: FacetSpec, packed: PackedFacets | None,
+                  counts, n_rows: int | None = None
+                  ) -> list[FacetCounts | None]:
+    """counts [R, F] (the rows of `packed`, any integer array-like) ->
+    one FacetCounts or None per batch row, in the caller's names and
+    order: the permutation back from pack_facets' sorting."""
+    n = len(spec.domains) if n_rows is None else n_rows
+    out: list[FacetCounts | None] = [None] * n
+    if packed is None:
+        return out
+    c = np.asarray(counts).astype(np.int64).reshape(len(packed.rows), -1)
+    E, L = len(packed.edges), len(packed.langs)
+    sl = facet_slots(E, L)
+    lang_at = {code: i for i, code in enumerate(packed.langs)}
+    for r, (b, hashes) in enumerate(zip(packed.rows, packed.lists)):
+        if b >= n:
+            continue
+        dom_at = {h: i for i, h in enumerate(hashes)}
+        out[b] = FacetCounts(
+            total=int(c[r, sl["total"]]),
+            date_zero=int(c[r, sl["date_zero"]]),
+            dates=tuple(int(v) for v in
+                        c[r, sl["date0"]:sl["date0"] + E + 1]),
+            languages={name: int(c[r, sl["lang0"] + lang_at[lang16(name)]])
+                       for name in spec.languages},
+            language_zero=int(c[r, sl["lang_zero"]]),
+            language_other=int(c[r, sl["lang_other"]]),
+            domains={name: int(c[r, sl["dom0"] + dom_at[domain_hash(name)]])
+                     for name in spec.domains[b]})
+    return out
+
+
+def facet_counts_np(scores: np.ndarray, fail: np.ndarray | None,
+                    attrs: np.ndarray, packed: PackedFacets) -> np.ndarray:
+    """The counts in numpy, for CpuShard: scores [B, N], fail bool
+    [B, N] or None, attrs [N, 4] -> [R, F] int32, by the rules of
+    FacetSpec and the layout of facet_slots."""
+    a = np.ascontiguousarray(attrs).view(np.uint32).reshape(-1, 4)
+    E, L = len(packed.edges), len(packed.langs)
+    sl = facet_slots(E, L)
+    edges = np.asarray(packed.edges, dtype=np.uint32)
+    code = a[:, 1] & np.uint32(LANG_MASK)
+    date = np.where(a[:, 0] == 0, sl["date_zero"],
+                    sl["date0"] + np.searchsorted(edges, a[:, 0],
+                                                  side="right"))
+    lang = np.full(len(a), sl["lang_other"], dtype=np.int64)
+    for i, c in enumerate(packed.langs):
+        lang[code == np.uint32(c)] = sl["lang0"] + i
+    lang[code == 0] = sl["lang_zero"]
+    F = packed.width
+    out = np.zeros((len(packed.rows), F), dtype=np.int64)
+    for r, (b, hashes) in enumerate(zip(packed.rows, packed.lists)):
+        m = scores[b] > 0
+        if fail is not None:
+            m &= ~fail[b]
+        out[r, sl["total"]] = m.sum()
+        out[r] += np.bincount(date[m], minlength=F)
+        out[r] += np.bincount(lang[m], minlength=F)
+        for i, h in enumerate(hashes):
+            out[r, sl["dom0"] + i] = (m & (a[:, 2] == np.uint32(h))).sum()
+    return out.astype(np.int32)
+
+
 def _is_packed_sets(f) -> bool:
     """(words4, allow_hashes, block_hashes), the form pack_pred_sets
     returns and the query plane forwards between ranks."""

@@ -33,7 +33,8 @@ import numpy as np
 import torch
 
 from ..hashing import hash64
-from .doc_attrs import (DEAD_BIT, DocFilter, TermOps, pack_pred,
+from .doc_attrs import (DEAD_BIT, DocFilter, FacetSpec, TermOps,
+                        facet_counts_np, pack_facets, pack_pred,
                         pack_pred_sets, passes, words_i32)
 
 BM25_K1 = 1.2
@@ -90,6 +91,9 @@ class ShardHits:
     bm25_ids: torch.Tensor      # [B, k] i64 (-1 pad)
     dense_scores: torch.Tensor  # [B, k] f32
     dense_ids: torch.Tensor     # [B, k] i64
+    # [R, F] i32 facet counts of the rows a FacetSpec names (layout:
+    # ops/csrc/facets.hip); None when the caller asked for none
+    facets: torch.Tensor | None = None
 
 
 @dataclass
@@ -816,6 +820,29 @@ class GpuShard:
         term_ops: one TermOps or None per query; a row with operands
         selects among the documents that hold every required and no
         excluded term, and masks the batch like a filter does."""
+        return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
+                                _mask, term_ops, None)[:2]
+
+    def search_bm25_facets(self, queries_terms: list[np.ndarray], k: int,
+                           facets, scores_buf: torch.Tensor | None = None,
+                           mark=None, filters=None, _mask=None,
+                           term_ops=None
+                           ) -> tuple[torch.Tensor, torch.Tensor,
+                                      torch.Tensor | None]:
+        """search_bm25 that also counts facets over every matching
+        document of the rows `facets` names (a FacetSpec or
+        PackedFacets): -> (values, indices, counts [R, F] i32 or None
+        when no row is counted). The count kernel (csrc/facets.hip) runs
+        on this stream straight after the scores are written, over the
+        buffer the top-k reads, with the same mask; it changes neither
+        the mask nor the select, so an unmasked batch keeps the fused
+        pass-1 histogram."""
+        return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
+                                _mask, term_ops,
+                                pack_facets(facets, len(queries_terms)))
+
+    def _bm25_plane(self, queries_terms, k, scores_buf, mark, filters,
+                    _mask, term_ops, facets):
         import time as _time
         from ..ops import kernels as K
         if mark is None:
@@ -878,21 +905,30 @@ class GpuShard:
                 evt = self._h2d_evt = torch.cuda.Event()
             evt.record()
         tp = mark("shard.bm25", tp)
+        counts = None
+        if facets is not None:
+            rows_t, edges_t, langs_t, desc_t, doms_t = (
+                torch.from_numpy(t) for t in facets.tables())
+            counts = K.facet_counts(
+                scores, rows_t, self.attrs, edges_t, langs_t, desc_t,
+                doms_t, mask=None if mask is None else mask[0],
+                row_pred=None if mask is None else mask[1])
+            tp = mark("shard.facets", tp)
         if mask is None:
             out = topk(scores, k, ext_hist1=hist)
         else:
             out = topk(scores, k, mask=mask[0], row_pred=mask[1])
         mark("shard.bm25topk", tp)
         self._bm25_scores_buf = scores
-        return out
+        return out[0], out[1], counts
 
     def search(self, queries_terms: list[np.ndarray],
                query_emb: torch.Tensor | None, k: int = 100,
                scores_buf: torch.Tensor | None = None,
                phase_t: dict | None = None,
                filters: list[DocFilter | None] | None = None,
-               term_ops: list[TermOps | None] | None = None
-               ) -> ShardHits:
+               term_ops: list[TermOps | None] | None = None,
+               facets: FacetSpec | None = None) -> ShardHits:
         """Score all queries against this shard; returns fixed-size
         top-k with global ids (the per-peer result cap analogue,
         reference p2p/routing.py:48). filters: one DocFilter or None per
@@ -901,7 +937,10 @@ class GpuShard:
         -inf / id -1. term_ops: one TermOps or None per query; both
         planes return only documents that hold every required and no
         excluded term (a required id that is nowhere in the shard
-        leaves the row all padding)."""
+        leaves the row all padding). facets: a FacetSpec (or
+        PackedFacets); ShardHits.facets then holds the counts over every
+        matching document of the rows it names, and the hits are what
+        they are without it."""
         import time as _time
 
         def mark(name, t0):
@@ -919,9 +958,15 @@ class GpuShard:
         k = min(k, N)
         tp = _time.perf_counter()
         mask = self._mask_for(filters, B, term_ops)   # once for both planes
-        bm_vals, bm_idx = self.search_bm25(queries_terms, k,
-                                           scores_buf=scores_buf,
-                                           mark=mark, _mask=mask)
+        counts = None
+        if facets is None:
+            bm_vals, bm_idx = self.search_bm25(queries_terms, k,
+                                               scores_buf=scores_buf,
+                                               mark=mark, _mask=mask)
+        else:
+            bm_vals, bm_idx, counts = self.search_bm25_facets(
+                queries_terms, k, facets, scores_buf=scores_buf, mark=mark,
+                _mask=mask)
         tp = _time.perf_counter()
 
         # --- dense plane ---
@@ -935,7 +980,7 @@ class GpuShard:
         return ShardHits(bm25_scores=bm_vals,
                          bm25_ids=self.to_global(bm_idx),
                          dense_scores=dn_vals,
-                         dense_ids=self.to_global(dn_idx))
+                         dense_ids=self.to_global(dn_idx), facets=counts)
 
     def search_dense(self, query_emb: torch.Tensor, k: int,
                      mark=None, filters=None, _mask=None, term_ops=None
@@ -1120,7 +1165,7 @@ class CpuShard(GpuShard):
 
     def search(self, queries_terms, query_emb, k: int = 100,
                scores_buf=None, phase_t=None, filters=None,
-               term_ops=None) -> ShardHits:
+               term_ops=None, facets=None) -> ShardHits:
         B = len(queries_terms)
         N = self.n_docs
         assert N > 0, "shard is empty"
@@ -1146,6 +1191,12 @@ class CpuShard(GpuShard):
         st = torch.from_numpy(scores)
         fail = self._fail_rows(filters, B, term_ops)
         bm_vals, bm_idx = self._masked_topk(st, fail, k)
+        counts = None
+        packed = pack_facets(facets, B)
+        if packed is not None:
+            counts = torch.from_numpy(facet_counts_np(
+                scores, None if fail is None else fail.numpy(),
+                self.attrs.numpy(), packed))
         if query_emb is not None and self.embeddings is not None:
             d_scores = query_emb.float().cpu() @ self.embeddings.float().T
             dn_vals, dn_idx = self._masked_topk(d_scores, fail, k)
@@ -1160,4 +1211,4 @@ class CpuShard(GpuShard):
 
         return ShardHits(bm25_scores=bm_vals, bm25_ids=to_global(bm_idx),
                          dense_scores=dn_vals.float(),
-                         dense_ids=to_global(dn_idx))
+                         dense_ids=to_global(dn_idx), facets=counts)

@@ -41,8 +41,14 @@ class Handlers:
                    domain_allowlist: list[str] | None = None,
                    domain_blocklist: list[str] | None = None,
                    fetch_full_content: bool = False,
-                   validate: bool = False,
+                   validate: bool = False, facets: bool = False,
+                   facet_domains: list[str] | None = None,
                    **_) -> dict[str, Any]:
+        """facets: add "total_matches" and "facets" (counts over every
+        matching document when the engine serves the query, see
+        AppContext.search); facet_domains: exact domains to count. Both
+        fields are null when the domain lists went over the cap and the
+        hits were filtered after an unfiltered search."""
         if not query or not query.strip():
             raise InfoMeshError("SRCH001", "empty query")
         # Reference-style argument forms (infomesh mcp/tools.py:53-136):
@@ -73,6 +79,8 @@ class Handlers:
         # are the true top of the passing documents. The lists keep
         # their suffix semantics (python.org admits docs.python.org):
         # the store expands each name to the exact domains it holds.
+        fkw = {"facets": True, "facet_domains": list(facet_domains or ())} \
+            if facets else {}
         include = exclude = None
         if domain_allowlist:
             # nothing stored under an allowed name: keep the names, which
@@ -86,12 +94,15 @@ class Handlers:
                 "web_search: %d domains after expansion, over the cap of "
                 "%d; over-fetching and filtering the hits instead",
                 len(include or ()) + len(exclude or ()), MAX_LIST_HASHES)
+            # no facets here: the search runs WITHOUT the lists, so its
+            # counts would cover documents the hits below are filtered
+            # down from; the answer carries null for both fields
             resp = self.ctx.search(query, limit=limit * 2, mode=mode)
         else:
             resp = self.ctx.search(query, limit=limit, mode=mode,
                                    include_domains=include,
                                    exclude_domains=exclude,
-                                   recency_days=recency_days)
+                                   recency_days=recency_days, **fkw)
         results = [result_to_dict(r) for r in resp.results]
         # the post-filter stays as a guard; it drops nothing the search
         # already filtered
@@ -136,6 +147,9 @@ class Handlers:
             "degraded": resp.degraded,
             "results": results,
         }
+        if facets:
+            out["total_matches"] = resp.total_matches
+            out["facets"] = resp.facets
         if validate:
             out["validation"] = self._cross_validate(query, results)
         if chunk_size:

@@ -30,6 +30,13 @@ TOOLS: list[dict] = [
                 "domain_blocklist": {"type": "array",
                                      "items": {"type": "string"}},
                 "fetch_full_content": {"type": "boolean"},
+                "facets": {"type": "boolean",
+                           "description": "add total_matches and facet "
+                                          "counts over every matching "
+                                          "document"},
+                "facet_domains": {"type": "array",
+                                  "items": {"type": "string"},
+                                  "description": "exact domains to count"},
                 "explain": {"type": "boolean"},
                 "chunk_size": {"type": "integer"},
                 "answer_mode": {

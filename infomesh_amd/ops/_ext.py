@@ -110,13 +110,25 @@ _SIGNATURES: dict[str, list] = {
                              c_void_p, c_int, c_long, c_int, c_void_p],
     "infomesh_topk_pruned_workspace_u32": [c_int, c_long, c_int, c_int],
     "infomesh_topk_pruned_zero_u32": [c_int],
+    "infomesh_facet_counts": [c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_long, c_void_p, c_int, c_int,
+                              c_long, c_long, c_int, c_int, c_int, c_int,
+                              c_void_p],
+    "infomesh_facet_chunk_docs": [],
+    "infomesh_facet_width": [c_int, c_int, c_int],
+    "infomesh_facet_slot": [c_int, c_int, c_int],
 }
 
 # Everything not listed here returns void. topk_*_u32: lengths;
 # dense_scores, gemm_bf16_nt_bmax: dispatch eligibility (0 = launched);
 # gemm_tile: tile code; gemm_bmax_width: columns per block maximum;
-# term_block_docs: documents per workgroup of term_bitmask.
+# term_block_docs: documents per workgroup of term_bitmask; facet_*: the
+# chunk size and the slot layout of facet_counts.
 _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
+             "infomesh_facet_chunk_docs": c_int,
+             "infomesh_facet_width": c_int,
+             "infomesh_facet_slot": c_int,
              "infomesh_topk_zero_u32": c_long,
              "infomesh_topk_pruned_workspace_u32": c_long,
              "infomesh_topk_pruned_zero_u32": c_long,

@@ -563,6 +563,126 @@ def term_bitmask(base_bits: torch.Tensor, src_row: torch.Tensor,
     return out
 
 
+FACET_MAX_EDGES = 7     # design limits of csrc/facets.hip
+FACET_MAX_LANGS = 32
+FACET_MAX_DOMS = 64
+_FACET_GROUPS = ("total", "date_zero", "date0", "lang_zero", "lang0",
+                 "lang_other", "dom0")
+
+
+def facet_chunk_docs() -> int:
+    """Documents per workgroup of facet_counts (FACET_CHUNK)."""
+    return int(_ext.lib().infomesh_facet_chunk_docs())
+
+
+def facet_slots(E: int, L: int) -> dict[str, int]:
+    """First slot of every group of a facet_counts row, as the extension
+    reports them (the layout is written down in csrc/facets.hip)."""
+    lib = _ext.lib()
+    return {name: int(lib.infomesh_facet_slot(i, E, L))
+            for i, name in enumerate(_FACET_GROUPS)}
+
+
+def facet_width(E: int, L: int, Dw: int) -> int:
+    """Row width F of facet_counts' result."""
+    return int(_ext.lib().infomesh_facet_width(E, L, Dw))
+
+
+def _host_words(t: torch.Tensor, name: str) -> torch.Tensor:
+    assert t.dtype == torch.int32 and t.is_contiguous(), \
+        f"{name}: contiguous i32"
+    return t.cpu()
+
+
+def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
+                 attrs: torch.Tensor, edges: torch.Tensor,
+                 langs: torch.Tensor, dom_desc: torch.Tensor,
+                 doms: torch.Tensor, mask: torch.Tensor | None = None,
+                 row_pred: torch.Tensor | None = None) -> torch.Tensor:
+    """Facet counts over every matching document (csrc/facets.hip, where
+    the match rule and the slot layout are written down): scores [B, N]
+    f32, attrs [N, 4] i32 and, with a mask, mask [P, W] i32 + row_pred
+    [B] i32 as TopK takes them, on the device. rows [R] i32 names the
+    batch rows to count; edges [E] and langs [L] hold u32 words as i32,
+    ascending as unsigned (langs unique); dom_desc [R, 2] i32 is (off, n)
+    of each counted row's list in doms, the flat i32 array of u32 domain
+    hashes, each list unique and ascending as unsigned. Returns counts
+    [R, F] i32, F = facet_width(E, L, max n); slots per facet_slots.
+
+    rows, edges, langs, dom_desc and doms are checked here, on the host,
+    before the kernel indexes with them: hand them over as host tensors
+    (they are then uploaded, no sync) or as device tensors (copied back
+    to check). More than 7 edges, 32 languages or 64 hashes in one list
+    is a ValueError, and nothing is launched."""
+    _check(scores, torch.float32, "scores")
+    _check(attrs, torch.int32, "attrs")
+    assert scores.dim() == 2
+    B, N = scores.shape
+    assert N >= 1 and attrs.shape == (N, 4), "attrs: [N, 4]"
+    assert (mask is None) == (row_pred is None), \
+        "mask and row_pred go together"
+    W = P = 0
+    if mask is not None:
+        _check(mask, torch.int32, "mask")
+        _check(row_pred, torch.int32, "row_pred")
+        assert mask.dim() == 2 and mask.shape[1] * 32 >= N
+        assert row_pred.numel() == B
+        P, W = mask.shape
+    h_rows = _host_words(rows, "rows")
+    h_edges = _host_words(edges, "edges")
+    h_langs = _host_words(langs, "langs")
+    h_desc = _host_words(dom_desc, "dom_desc")
+    h_doms = _host_words(doms, "doms")
+    assert h_rows.dim() == 1 and h_edges.dim() == 1 and h_langs.dim() == 1 \
+        and h_doms.dim() == 1
+    R, E, L = h_rows.numel(), h_edges.numel(), h_langs.numel()
+    assert 1 <= R and h_desc.shape == (R, 2), "dom_desc: [R, 2]"
+    off, n = h_desc[:, 0].long(), h_desc[:, 1].long()
+    assert bool((n >= 0).all()) and bool((off >= 0).all()) \
+        and bool((off + n <= h_doms.numel()).all()), \
+        "dom_desc points outside doms"
+    Dw = int(n.max())
+    if E > FACET_MAX_EDGES or L > FACET_MAX_LANGS or Dw > FACET_MAX_DOMS:
+        raise ValueError(
+            f"facets: {E} date edges, {L} languages, {Dw} domains in one "
+            f"list; the caps are {FACET_MAX_EDGES}, {FACET_MAX_LANGS} and "
+            f"{FACET_MAX_DOMS}")
+    assert bool((h_rows >= 0).all()) and bool((h_rows < B).all()), \
+        "rows points outside the batch"
+
+    def asc(t, strict):
+        u = t.long() & 0xFFFFFFFF
+        d = u.diff()
+        return bool((d > 0).all()) if strict else bool((d >= 0).all())
+    assert asc(h_edges, False), "edges: ascending as unsigned"
+    assert asc(h_langs, True), "langs: ascending and unique"
+    assert all(asc(h_doms[o:o + c], True)
+               for o, c in zip(off.tolist(), n.tolist())), \
+        "doms: every list ascending as unsigned and unique"
+    assert (N + facet_chunk_docs() - 1) // facet_chunk_docs() <= 65535
+    dev = scores.device
+    tables = (dom_desc, rows, edges, langs, doms)
+    if not any(t.is_cuda for t in tables):
+        # one upload for the five host tables; dom_desc first, so that
+        # its (off, n) pairs stay 8-byte aligned
+        flat = torch.cat([t.reshape(-1) for t in tables]).to(
+            dev, non_blocking=True)
+        desc_d, rows_d, edges_d, langs_d, doms_d = flat.split(
+            [t.numel() for t in tables])
+    else:
+        desc_d, rows_d, edges_d, langs_d, doms_d = (
+            t if t.is_cuda else t.to(dev, non_blocking=True) for t in tables)
+    F = facet_width(E, L, Dw)
+    counts = torch.zeros((R, F), device=dev, dtype=torch.int32)
+    _ext.lib().infomesh_facet_counts(
+        scores.data_ptr(), rows_d.data_ptr(), _ptr(mask), _ptr(row_pred),
+        attrs.data_ptr(), edges_d.data_ptr() if E else None,
+        langs_d.data_ptr() if L else None, desc_d.data_ptr(),
+        doms_d.data_ptr() if doms_d.numel() else None, doms_d.numel(),
+        counts.data_ptr(), B, R, N, W, P, E, L, F, _ext.stream_ptr())
+    return counts
+
+
 def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
                qt_off: torch.Tensor, qt_ut: torch.Tensor,
                qt_idf: torch.Tensor, u_begin: torch.Tensor,

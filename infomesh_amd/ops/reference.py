@@ -220,6 +220,41 @@ def term_bitmask(base_bits: torch.Tensor, src_row: torch.Tensor,
     return torch.from_numpy(np.stack(rows).view(np.int32).reshape(-1, W))
 
 
+def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
+                 attrs: torch.Tensor, edges: torch.Tensor,
+                 langs: torch.Tensor, dom_desc: torch.Tensor,
+                 doms: torch.Tensor, mask: torch.Tensor | None = None,
+                 row_pred: torch.Tensor | None = None) -> torch.Tensor:
+    """Oracle of csrc/facets.hip, same arguments as kernels.facet_counts:
+    document d matches batch row b = rows[r] iff its bit is set in
+    mask[row_pred[b]] (no mask: every document) and scores[b, d] > 0; a
+    match adds 1 to TOTAL, to one date slot, to one language slot and to
+    at most one domain slot of counts[r]. The rules are written in numpy
+    once, in index/doc_attrs.facet_counts_np, which CpuShard counts
+    with as well; this function only unpacks the kernel's arguments
+    (bit rows, descriptors) for it. Returns counts [R, F] i32."""
+    import numpy as np
+    from ..index.doc_attrs import PackedFacets, facet_counts_np
+    s = scores.detach().float().cpu().numpy()
+    B, N = s.shape
+    h = doms.cpu().numpy().view(np.uint32)
+    desc = dom_desc.cpu().numpy().astype(np.int64).reshape(-1, 2)
+    packed = PackedFacets(
+        edges=tuple(int(v) for v in edges.cpu().numpy().view(np.uint32)),
+        langs=tuple(int(v) for v in langs.cpu().numpy().view(np.uint32)),
+        rows=tuple(int(b) for b in rows.cpu().numpy()),
+        lists=tuple(tuple(int(v) for v in h[off:off + n])
+                    for off, n in desc))
+    fail = None
+    if mask is not None:
+        words = mask.cpu().numpy().view(np.uint32)
+        ok = np.unpackbits(words.view(np.uint8), axis=1,
+                           bitorder="little")[:, :N].astype(bool)
+        fail = ~ok[row_pred.cpu().numpy().astype(np.int64)]
+    return torch.from_numpy(facet_counts_np(s, fail, attrs.cpu().numpy(),
+                                            packed))
+
+
 def masked_topk(scores: torch.Tensor, k: int, bits: torch.Tensor,
                 row_pred: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Oracle of the masked top-k: failing columns become -inf, then

@@ -19,7 +19,8 @@ import numpy as np
 import torch
 
 from ..index.doc_attrs import (HAS_ALLOW_BIT, HAS_BLOCK_BIT, U32_MAX,
-                               TermOps, pack_pred_sets)
+                               FacetSpec, PackedFacets, TermOps,
+                               pack_facets, pack_pred_sets)
 from ..index.gpu_index import GpuShard, ShardHits
 from .fabric import Fabric
 
@@ -34,6 +35,11 @@ MAX_QUERY_TERMS = 32
 _PRED_COLS = 2
 _HAS_FILTER = 1 << 17
 _HAS_LISTS = HAS_ALLOW_BIT | HAS_BLOCK_BIT
+# Bit 20 of ROW 0's z marks a batch that carries a FacetSpec: the spec
+# belongs to the batch, not to a row, and row 0 always exists. It is
+# stripped before the predicates are unpacked, and only such a batch is
+# followed by the two broadcasts of _broadcast_facets.
+_HAS_FACETS = 1 << 20
 # Term operands (TermOps) ride in the same broadcast, as flag bits on the
 # row's term entries; term ids are below 2^17, so bits 40.. are free. A
 # require operand is its scoring term with bit 40 set, an exclude operand
@@ -95,6 +101,10 @@ class FusedHits:
     dense_ids: torch.Tensor
     dense_scores: torch.Tensor
     degraded: bool = False   # served by a shrunk rank group
+    # [R, F] i32 facet counts summed over the shards, one row per row the
+    # FacetSpec names (doc_attrs.facet_results maps them back); None
+    # when the batch had no spec
+    facets: torch.Tensor | None = None
 
 
 def rrf_fuse(ids_lists: list[torch.Tensor], score_lists: list[torch.Tensor],
@@ -186,21 +196,29 @@ class DistributedQueryPlane:
                      encode_fn=None,
                      encode_shard=None,
                      filters: list | None = None,
-                     term_ops: list | None = None) -> FusedHits | None:
+                     term_ops: list | None = None,
+                     facets: FacetSpec | None = None) -> FusedHits | None:
         """filters (rank 0): one DocFilter or None per row; every shard
         applies them in its top-k selection. term_ops (rank 0): one
-        TermOps or None per row, honoured by every shard alike.
+        TermOps or None per row, honoured by every shard alike. facets
+        (rank 0): a FacetSpec; every shard counts its matching documents
+        for the rows it names and FusedHits.facets holds the sums.
 
         Collective search with rank-fault tolerance: on a collective
         failure (dead rank → timeout) the fabric shrinks to the
         pre-created exclusion subgroup and the batch retries once,
         flagged degraded (reference parity: local-only serving when
         peers are absent, infomesh/search/query.py:471-490)."""
+        if facets is not None:
+            # packed once, before any collective: over a cap is a
+            # ValueError on rank 0 alone, with nothing sent; the retry
+            # below carries the packed spec along
+            facets = pack_facets(facets, B)
         try:
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
                                       encode_fn, encode_shard, filters,
-                                      term_ops)
+                                      term_ops, facets)
         except RuntimeError as e:
             if not self.fabric.initialized or not self.fabric.collective_ok:
                 raise
@@ -234,7 +252,7 @@ class DistributedQueryPlane:
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
                                       encode_fn, encode_shard, filters,
-                                      term_ops)
+                                      term_ops, facets)
 
     def _sharded_encode(self, encode_shard: dict, B: int,
                         dim: int) -> torch.Tensor:
@@ -274,7 +292,7 @@ class DistributedQueryPlane:
                       use_dense: bool = True,
                       phase_t: dict | None = None,
                       encode_fn=None, encode_shard=None, filters=None,
-                      term_ops=None) -> FusedHits | None:
+                      term_ops=None, facets=None) -> FusedHits | None:
         """One collective search attempt. Rank 0 passes real queries and
         gets the FusedHits; other ranks pass None and get None.
 
@@ -301,11 +319,12 @@ class DistributedQueryPlane:
                                            phase_t=phase_t,
                                            encode_shard=encode_shard,
                                            filters=filters,
-                                           term_ops=term_ops)
+                                           term_ops=term_ops,
+                                           facets=facets)
             tp = mark("plane.shard", tp)
         else:
-            terms, filters, term_ops = self._broadcast_query(
-                queries_terms, B, filters, term_ops)
+            terms, filters, term_ops, facets = self._broadcast_query(
+                queries_terms, B, filters, term_ops, facets)
             if encode_shard is not None:
                 emb = self._sharded_encode(encode_shard, B, dim).float()
             else:
@@ -320,7 +339,7 @@ class DistributedQueryPlane:
             hits = self.shard.search(
                 terms, emb if use_dense else None, k=self.k,
                 scores_buf=self._get_scores_buf(B), phase_t=phase_t,
-                filters=filters, term_ops=term_ops)
+                filters=filters, term_ops=term_ops, facets=facets)
             tp = mark("plane.shard", tp)
         # ONE packed all-gather instead of four: xGMI collectives at
         # this payload size (a few hundred KB) are latency-dominated,
@@ -340,6 +359,13 @@ class DistributedQueryPlane:
         # view(int64) then raises. _as_i64 guarantees offset-0 storage.
         bm_i = _as_i64(g[:, :, 2 * k_:4 * k_])
         dn_i = _as_i64(g[:, :, 4 * k_:6 * k_])
+        facet_sum = None
+        if hits.facets is not None:
+            # counts are additive over shards: one more all-gather, only
+            # for a batch with a spec (every rank holds the same one, so
+            # all of them take this branch together)
+            facet_sum = self.fabric.all_gather(
+                hits.facets.to(self.fabric.device)).sum(0).to(torch.int32)
         tp = mark("plane.gather", tp)
         if self.fabric.rank != 0:
             return None
@@ -373,12 +399,12 @@ class DistributedQueryPlane:
         return FusedHits(ids=ids, scores=scores, bm25_ids=bm_i,
                          bm25_scores=bm_s, dense_ids=dn_i,
                          dense_scores=dn_s,
-                         degraded=self.fabric.degraded)
+                         degraded=self.fabric.degraded, facets=facet_sum)
 
     def _search_overlapped(self, queries_terms, query_emb, encode_fn,
                            B, dim, use_dense, phase_t=None,
                            encode_shard=None, filters=None,
-                           term_ops=None) -> ShardHits:
+                           term_ops=None, facets=None) -> ShardHits:
         """BM25 on a side stream || query encoding on the main stream.
 
         Broadcast order (terms, then embeddings) is identical on all
@@ -401,8 +427,8 @@ class DistributedQueryPlane:
             self._bm25_stream = torch.cuda.Stream(dev)
         # terms must be broadcast before any rank's shard work
         tp = _time.perf_counter()
-        terms, filters, term_ops = self._broadcast_query(
-            queries_terms, B, filters, term_ops)
+        terms, filters, term_ops, facets = self._broadcast_query(
+            queries_terms, B, filters, term_ops, facets)
         tp = mark("ov.terms", tp)
         main = torch.cuda.current_stream(dev)
         mask = None
@@ -413,10 +439,19 @@ class DistributedQueryPlane:
             for t in mask or ():
                 t.record_stream(self._bm25_stream)
         self._bm25_stream.wait_stream(main)
+        counts = None
         with torch.cuda.stream(self._bm25_stream):
-            bm_vals, bm_idx = self.shard.search_bm25(
-                terms, self.k, scores_buf=self._get_scores_buf(B),
-                filters=filters, _mask=mask)
+            if facets is None:
+                bm_vals, bm_idx = self.shard.search_bm25(
+                    terms, self.k, scores_buf=self._get_scores_buf(B),
+                    filters=filters, _mask=mask)
+            else:
+                # the counts ride the side stream with the scores they
+                # read; main waits for that stream before the gathers
+                bm_vals, bm_idx, counts = self.shard.search_bm25_facets(
+                    terms, self.k, facets,
+                    scores_buf=self._get_scores_buf(B), filters=filters,
+                    _mask=mask)
             bm_ids = self.shard.to_global(bm_idx)
         tp = mark("ov.bm25", tp)
         if encode_shard is not None:
@@ -442,26 +477,31 @@ class DistributedQueryPlane:
             dn_ids = torch.full((B, k), -1, device=dev, dtype=torch.int64)
         main.wait_stream(self._bm25_stream)
         return ShardHits(bm25_scores=bm_vals, bm25_ids=bm_ids,
-                         dense_scores=dn_vals, dense_ids=dn_ids)
+                         dense_scores=dn_vals, dense_ids=dn_ids,
+                         facets=counts)
 
     def _broadcast_terms(self, queries_terms, B, filters=None):
         """-> (terms, filters) of a batch without term operands."""
         return self._broadcast_query(queries_terms, B, filters)[:2]
 
     def _broadcast_query(self, queries_terms, B, filters=None,
-                         term_ops=None):
-        """-> (terms, filters, term_ops) as every rank must see them. At
-        world > 1 the predicates ride in the one terms broadcast (packed
-        words, which the shards accept in place of DocFilter objects),
-        and so do the term operands, as flag bits on the term entries
-        (pack_term_row). term_ops comes back None when no row has an
-        operand."""
+                         term_ops=None, facets=None):
+        """-> (terms, filters, term_ops, facets) as every rank must see
+        them. At world > 1 the predicates ride in the one terms broadcast
+        (packed words, which the shards accept in place of DocFilter
+        objects), and so do the term operands, as flag bits on the term
+        entries (pack_term_row). term_ops comes back None when no row
+        has an operand. facets (rank 0: a FacetSpec or PackedFacets)
+        comes back as PackedFacets, or None when no row is counted; the
+        terms broadcast only announces it (_HAS_FACETS), the spec itself
+        follows in _broadcast_facets."""
         if term_ops is not None and not any(term_ops):
             term_ops = None
+        facets = pack_facets(facets, B)
         if self.fabric.world == 1 and queries_terms is not None:
             # no collective needed: skip the pack + GPU round-trip +
             # device sync entirely
-            return queries_terms, filters, term_ops
+            return queries_terms, filters, term_ops, facets
         dev = self.fabric.device
         T = MAX_QUERY_TERMS
         terms_t = torch.full((B, T + _PRED_COLS), -1, dtype=torch.int64)
@@ -481,10 +521,18 @@ class DistributedQueryPlane:
                     if allow or block:
                         lists[i] = (allow, block)
                 terms_t[:, T:] = torch.from_numpy(cols.view(np.int64))
+            if facets is not None:
+                terms_t[0, T + 1] |= _HAS_FACETS
         terms_t = terms_t.to(dev)
         self.fabric.broadcast(terms_t)
         tt = terms_t.cpu().numpy()
         cols = np.ascontiguousarray(tt[:, T:]).view(np.uint64)
+        # the batch's facet mark, stripped before the predicates are
+        # unpacked: row 0 keeps its own words, filtered or not
+        has_facets = bool(cols[0, 1] & np.uint64(_HAS_FACETS))
+        cols[0, 1] &= ~np.uint64(_HAS_FACETS)
+        if has_facets:
+            facets = self._broadcast_facets(facets)
         has = (cols[:, 1] & np.uint64(_HAS_FILTER)) != 0
         filters = None
         if has.any():
@@ -500,7 +548,43 @@ class DistributedQueryPlane:
         rows = [unpack_term_row(tt[i, :T]) for i in range(B)]
         term_ops = [ops for _, ops in rows]
         return ([terms for terms, _ in rows], filters,
-                term_ops if any(term_ops) else None)
+                term_ops if any(term_ops) else None,
+                facets if has_facets else None)
+
+    def _broadcast_facets(self, packed: PackedFacets | None) -> PackedFacets:
+        """The spec of a batch whose terms broadcast announced one, in
+        two broadcasts: a fixed-shape header (E, L, R, number of
+        hashes), then one flat array: edges, language codes, counted
+        rows, each row's list length, all the hashes. Rank 0 passes its
+        PackedFacets; every rank returns the same one."""
+        dev = self.fabric.device
+        head = torch.zeros(4, dtype=torch.int64)
+        flat: list[int] = []
+        if packed is not None:
+            hashes = [h for lst in packed.lists for h in lst]
+            head = torch.tensor([len(packed.edges), len(packed.langs),
+                                 len(packed.rows), len(hashes)],
+                                dtype=torch.int64)
+            flat = [*packed.edges, *packed.langs, *packed.rows,
+                    *(len(lst) for lst in packed.lists), *hashes]
+        head = head.to(dev)
+        self.fabric.broadcast(head)
+        E, L, R, H = head.cpu().tolist()
+        body = (torch.tensor(flat, dtype=torch.int64) if packed is not None
+                else torch.zeros(E + L + 2 * R + H, dtype=torch.int64))
+        body = body.to(dev)
+        self.fabric.broadcast(body)
+        v = body.cpu().tolist()
+        edges, langs = v[:E], v[E:E + L]
+        rows = v[E + L:E + L + R]
+        lens = v[E + L + R:E + L + 2 * R]
+        at = E + L + 2 * R
+        lists = []
+        for n in lens:
+            lists.append(tuple(v[at:at + n]))
+            at += n
+        return PackedFacets(edges=tuple(edges), langs=tuple(langs),
+                            rows=tuple(rows), lists=tuple(lists))
 
     def _broadcast_lists(self, filters: list, lists: dict, B: int) -> None:
         """The domain lists of a batch whose flag bits announce some:

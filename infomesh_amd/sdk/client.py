@@ -13,7 +13,8 @@ DEFAULT_BASE = "http://127.0.0.1:8080"
 
 
 def _search_params(query, limit, mode, include_domains, exclude_domains,
-                   recency_days) -> dict[str, Any]:
+                   recency_days, facets=False,
+                   facet_domains=None) -> dict[str, Any]:
     """/search parameters; the domain lists go comma-separated, and only
     when given."""
     params: dict[str, Any] = {"q": query, "limit": limit, "mode": mode}
@@ -23,7 +24,21 @@ def _search_params(query, limit, mode, include_domains, exclude_domains,
         params["exclude_domains"] = ",".join(exclude_domains)
     if recency_days:
         params["recency_days"] = recency_days
+    if facets:
+        params["facets"] = 1
+        if facet_domains:
+            params["facet_domains"] = ",".join(facet_domains)
     return params
+
+
+def _search_result(body: dict, facets: bool):
+    """The hit list, as ever; for a request with facets the hits with
+    the counts: {"results", "total_matches", "facets"}."""
+    if not facets:
+        return body["results"]
+    return {"results": body["results"],
+            "total_matches": body.get("total_matches"),
+            "facets": body.get("facets")}
 
 
 class InfoMeshClient:
@@ -36,14 +51,18 @@ class InfoMeshClient:
 
     def search(self, query: str, limit: int = 10, mode: str = "auto",
                include_domains=None, exclude_domains=None,
-               recency_days: float = 0) -> list[dict[str, Any]]:
+               recency_days: float = 0, facets: bool = False,
+               facet_domains=None):
         """include_domains / exclude_domains: exact domains to allow /
-        block; recency_days: only documents crawled that recently."""
+        block; recency_days: only documents crawled that recently.
+        facets: return {"results", "total_matches", "facets"} instead of
+        the hit list, with counts over every matching document;
+        facet_domains: the domains to count."""
         r = self._client.get("/search", params=_search_params(
             query, limit, mode, include_domains, exclude_domains,
-            recency_days))
+            recency_days, facets, facet_domains))
         r.raise_for_status()
-        return r.json()["results"]
+        return _search_result(r.json(), facets)
 
     def status(self) -> dict[str, Any]:
         r = self._client.get("/status")
@@ -94,12 +113,14 @@ class AsyncInfoMeshClient:
 
     async def search(self, query: str, limit: int = 10, mode: str = "auto",
                      include_domains=None, exclude_domains=None,
-                     recency_days: float = 0) -> list[dict[str, Any]]:
+                     recency_days: float = 0, facets: bool = False,
+                     facet_domains=None):
+        """As InfoMeshClient.search."""
         r = await self._client.get("/search", params=_search_params(
             query, limit, mode, include_domains, exclude_domains,
-            recency_days))
+            recency_days, facets, facet_domains))
         r.raise_for_status()
-        return r.json()["results"]
+        return _search_result(r.json(), facets)
 
     async def status(self) -> dict[str, Any]:
         r = await self._client.get("/status")

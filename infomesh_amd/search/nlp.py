@@ -256,6 +256,37 @@ def with_filter_tokens(query: str, include=(), exclude=(),
     return " ".join(parts)
 
 
+# A facet request travels to the engine as one token at the end of the
+# query text, like the filters do: facets:@ and the domains to count,
+# comma-separated (facets:@ alone: no domain counts). No other code
+# reads or writes this syntax.
+_FACET_RE = re.compile(r"(?<!\S)facets:@(\S*)(?!\S)")
+
+
+def with_facet_token(query: str, domains=()) -> str:
+    """`query` with the token appended that parse_facet_token reads
+    back: the one writer of that syntax. Names are written as
+    with_filter_tokens writes a list's."""
+    names = _site_names(",".join(
+        re.sub(r"[\s,]+", "_", d.strip()) for d in domains or ()
+        if d and d.strip()))
+    return f"{query} facets:@{','.join(names)}".lstrip()
+
+
+def parse_facet_token(query: str) -> tuple[str, tuple[str, ...] | None]:
+    """(text without the token, domains to count) of a query
+    with_facet_token wrote; (query, None) when it carries no token."""
+    found: list[tuple[str, ...]] = []
+
+    def _sub(m: re.Match) -> str:
+        found.append(_site_names(m.group(1)))
+        return ""
+    text = _FACET_RE.sub(_sub, query)
+    if not found:
+        return query, None
+    return re.sub(r"\s{2,}", " ", text).strip(), found[-1]
+
+
 # ---------------------------------------------------- related searches
 
 @dataclass

@@ -49,6 +49,13 @@ class SearchResponse:
     expanded: list[str] = field(default_factory=list)
     degraded: bool = False
     total_candidates: int = 0
+    # only for a request with facets=True (AppContext.search):
+    # total_matches is the size of the whole match set on the GPU plane
+    # (None when FTS served the query), facets a dict with "scope"
+    # ("matches": counted over every matching document; "results": over
+    # the returned hits), "domains", "languages" and "date_ranges"
+    total_matches: int | None = None
+    facets: dict | None = None
 
 
 def preprocess_query(query: str, language: str = "en",

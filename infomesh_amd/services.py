@@ -9,6 +9,7 @@ path becomes a GPU-engine ingest (SURVEY.md §2.9 last row).
 from __future__ import annotations
 
 import logging
+import math
 import time
 from dataclasses import dataclass, field
 from typing import Any
@@ -23,14 +24,18 @@ from .crawler.scheduler import Scheduler
 from .crawler.worker import CrawlResult, CrawlWorker
 from .engine import HybridEngine
 from .errors import GpuExtensionMissing, InfoMeshError
-from .index.doc_attrs import DocFilter, pack_pred_sets
+from .crawler.lang_detect import known_languages
+from .index.doc_attrs import (FACET_MAX_DOMS, DocFilter, FacetCounts,
+                              FacetSpec, pack_pred_sets)
 from .index.gpu_index import bm25_term_ids
 from .index.link_graph import LinkGraph
 from .index.local_store import Document, LocalStore
 from .search.batcher import QueryBatcher
 from .search.cache import QueryCache
-from .search.nlp import (RelatedSearchTracker, parse_query_filters,
-                         parse_term_operators, with_filter_tokens)
+from .search.facets import compute_facets
+from .search.nlp import (RelatedSearchTracker, parse_facet_token,
+                         parse_query_filters, parse_term_operators,
+                         with_facet_token, with_filter_tokens)
 from .search.passage import fast_snippet
 from .search.query import (SearchResponse, preprocess_query,
                            search_hybrid, search_local)
@@ -46,6 +51,23 @@ log = logging.getLogger("infomesh.services")
 # required words compares the same tokens hashed into 2^62, where two
 # words do not meet in practice.
 _GUARD_VOCAB = 1 << 62
+
+# date facet: the reference's labels (infomesh/search/facets.py), oldest
+# first, as the buckets between the edges floor(now) - {365, 30, 7, 1}
+# days and floor(now) + 1 come out; a crawl time of 0 and one in the
+# future are both "unknown"
+_DATE_LABELS = ("older", "this_year", "this_month", "this_week", "today",
+                "unknown")
+_DATE_AGES_D = (365, 30, 7, 1)
+
+
+@dataclass
+class FacetedHits:
+    """What _batch_execute returns for a query that carried a facet
+    token: its hydrated hits (cut to the batch's limit, not the
+    caller's) and its counts over the whole match set."""
+    hits: list
+    counts: FacetCounts | None
 
 
 @dataclass
@@ -273,7 +295,8 @@ class AppContext:
                mode: str = "auto", use_cache: bool = True,
                deduct: bool = True, include_domains=None,
                exclude_domains=None,
-               recency_days: float = 0) -> SearchResponse:
+               recency_days: float = 0, facets: bool = False,
+               facet_domains=()) -> SearchResponse:
         """Unified search entry (reference mcp/handlers.py:382 flow):
         cache -> credits -> local/hybrid/distributed -> cache.
 
@@ -283,9 +306,27 @@ class AppContext:
         minute. All three travel as filter tokens in the query text, so
         they reach the cache key and whichever path serves the query.
         On the GPU plane one query's lists hold at most
-        doc_attrs.MAX_LIST_HASHES domains; more is a ValueError."""
+        doc_attrs.MAX_LIST_HASHES domains; more is a ValueError.
+
+        facets: also fill SearchResponse.total_matches and .facets.
+        Served by the engine, the counts cover EVERY document that
+        matches the query (passes its filters and operators and holds a
+        query term), on all shards: "scope": "matches", languages as
+        crawler/lang_detect knows them plus "unknown" and "other",
+        date_ranges by the reference's labels, and domains for the
+        names in facet_domains only (at most doc_attrs.FACET_MAX_DOMS,
+        more is a ValueError; they count by 32-bit hash). Served from
+        FTS, the counts cover the returned hits ("scope": "results")
+        and total_matches is None. A request without facets gets the
+        response it always got."""
         from .utils.plugins import GLOBAL_PLUGINS
         query = GLOBAL_PLUGINS.run("pre_search", query, mode=mode)
+        # facets:@... is the serving path's own syntax (_engine_search
+        # writes it, _batch_execute reads it): one typed into the query
+        # is dropped here, on the caller's thread, so that it neither
+        # asks for counts nobody reads nor reaches the shared batch.
+        # Facets are asked for with the `facets` parameter.
+        query = parse_facet_token(query)[0]
         if include_domains or exclude_domains or recency_days:
             after = None
             if recency_days:
@@ -294,7 +335,19 @@ class AppContext:
             query = with_filter_tokens(query, include_domains,
                                        exclude_domains, after)
         limit = limit or self.config.search.max_results
-        key = QueryCache.make_key(query, limit=limit, mode=mode)
+        fdoms = None
+        if facets:
+            fdoms = tuple(dict.fromkeys(
+                d.strip().lower() for d in facet_domains or ()
+                if d and d.strip()))
+            if len(fdoms) > FACET_MAX_DOMS:
+                raise ValueError(
+                    f"{len(fdoms)} facet domains; the cap is "
+                    f"{FACET_MAX_DOMS} per query")
+        # None leaves a plain request's key as it always was
+        key = QueryCache.make_key(query, limit=limit, mode=mode,
+                                  facets=None if fdoms is None
+                                  else list(fdoms))
         if use_cache:
             cached = self.cache.get(key)
             if cached is not None:
@@ -332,7 +385,8 @@ class AppContext:
                 # single-fusion path: the GPU plane RRF-fuses BM25 +
                 # dense exactly once; results are hydrated from the
                 # LocalStore (round-1 double-fusion fix)
-                resp = self._engine_search(query, limit, mode)
+                resp = self._engine_search(query, limit, mode,
+                                           facet_domains=fdoms)
             else:
                 resp = search_hybrid(
                     self.store, None, query, limit=limit,
@@ -345,6 +399,13 @@ class AppContext:
                     resp.mode = "distributed"
         else:
             raise InfoMeshError("SRCH001", f"unknown mode {mode!r}")
+        if fdoms is not None and resp.facets is None:
+            # FTS served it: SQLite hands back a LIMITed list, so the
+            # counts can only cover the hits
+            over = compute_facets(resp.results)
+            resp.facets = {"scope": "results", "domains": over["domains"],
+                           "languages": over["languages"],
+                           "date_ranges": over["dates"]}
         resp = GLOBAL_PLUGINS.run("post_search", resp, query=query)
         if use_cache:
             self.cache.put(key, resp)
@@ -394,6 +455,26 @@ class AppContext:
         if self.batcher is not None \
                 and self.batcher.engine is not self.engine:
             self.batcher.engine = self.engine   # engine was rebound
+        # a facet request travels as a token in the text too
+        # (nlp.with_facet_token): strip it, and build ONE spec for the
+        # batch, one `now`, the fixed language list, and a domain list
+        # per asking row. Rows that did not ask are not counted and get
+        # the plain list they always got. An error here would fail every
+        # caller of the batch, so a list over the cap (AppContext.search
+        # refuses one on the caller's thread; only a direct submit can
+        # bring one) is cut to its first FACET_MAX_DOMS names, never
+        # raised.
+        asked = [(text, doms if doms is None else doms[:FACET_MAX_DOMS])
+                 for text, doms in map(parse_facet_token, queries)]
+        queries = [text for text, _ in asked]
+        spec = None
+        if any(doms is not None for _, doms in asked):
+            now = math.floor(time.time())
+            spec = FacetSpec(
+                date_edges=tuple(now - d * 86400 for d in _DATE_AGES_D)
+                + (now + 1,),
+                languages=known_languages(),
+                domains=tuple(doms for _, doms in asked))
         filters = None
         parsed: list = [None] * len(queries)
         if self.config.gpu.filters:
@@ -419,13 +500,17 @@ class AppContext:
                 {int(i) for w in req
                  for i in bm25_term_ids(w, vocab=_GUARD_VOCAB)} or None
                 for _, req, _ in split]
-            per_q = self.engine.search_many(
-                queries, limit=limit, filters=filters,
-                require=[req for _, req, _ in split],
-                exclude=[exc for _, _, exc in split])
+            kw = dict(require=[req for _, req, _ in split],
+                      exclude=[exc for _, _, exc in split])
         else:
+            kw = {}
+        counts: list = [None] * len(queries)
+        if spec is None:
             per_q = self.engine.search_many(queries, limit=limit,
-                                            filters=filters)
+                                            filters=filters, **kw)
+        else:
+            per_q, counts = self.engine.search_with_facets(
+                queries, limit=limit, filters=filters, facets=spec, **kw)
         gids = [h.doc_id for hits in per_q for h in hits]
         docs = self.store.get_documents(gids)
         out: list[list] = []
@@ -465,12 +550,26 @@ class AppContext:
                     h.score += self.feedback.url_boost(h.url)
                 hydrated.sort(key=lambda x: x.score, reverse=True)
             out.append(hydrated)
-        return out
+        return [hits if doms is None else FacetedHits(hits, c)
+                for hits, c, (_, doms) in zip(out, counts, asked)]
 
-    def _engine_search(self, query: str, limit: int,
-                       mode: str) -> SearchResponse:
+    @staticmethod
+    def _facets_dict(c: FacetCounts) -> dict:
+        """FacetCounts of the serving spec (_batch_execute) -> the
+        "facets" dict of a SearchResponse."""
+        ranges = dict(zip(_DATE_LABELS, c.dates))
+        ranges["unknown"] += c.date_zero
+        langs = dict(c.languages)
+        langs["unknown"] = c.language_zero
+        langs["other"] = c.language_other
+        return {"scope": "matches", "domains": dict(c.domains),
+                "languages": langs, "date_ranges": ranges}
+
+    def _engine_search(self, query: str, limit: int, mode: str,
+                       facet_domains=None) -> SearchResponse:
         """GPU-plane search via the micro-batcher (fused once on the
-        plane, hydrated batch-wide in _batch_execute)."""
+        plane, hydrated batch-wide in _batch_execute). facet_domains:
+        None, or the domains to count of a request with facets."""
         t0 = time.time()
         trace = None
         if self.otlp is not None and self.otlp.enabled:
@@ -487,23 +586,38 @@ class AppContext:
             if self.config.gpu.filters:
                 text = parse_query_filters(text).text
             self.engine.term_ops_for(*parse_term_operators(text))
+        # The one place that writes the facet token, from the capped
+        # `facet_domains` alone and behind the preprocessed text, so
+        # that effective_query stays without it. Preprocessing passes a
+        # token through untouched, which is why AppContext.search drops
+        # a typed one first; one that still came this way goes here.
+        eff = parse_facet_token(eff)[0]
+        sent = eff if facet_domains is None \
+            else with_facet_token(eff, facet_domains)
         batcher = self.ensure_batcher()
         if trace is not None:
             with trace.span("engine"):
-                hits = (batcher.submit(eff, limit) if batcher is not None
-                        else self._batch_execute([eff], limit)[0])
+                hits = (batcher.submit(sent, limit) if batcher is not None
+                        else self._batch_execute([sent], limit)[0])
             self.otlp.export(trace)
         elif batcher is not None:
-            hits = batcher.submit(eff, limit)
+            hits = batcher.submit(sent, limit)
         else:
-            hits = self._batch_execute([eff], limit)[0]
-        return SearchResponse(
+            hits = self._batch_execute([sent], limit)[0]
+        counts = None
+        if isinstance(hits, FacetedHits):
+            hits, counts = hits.hits[:limit], hits.counts
+        resp = SearchResponse(
             query=query, effective_query=eff, results=hits,
             elapsed_ms=(time.time() - t0) * 1e3,
             mode="distributed" if mode == "distributed" else "hybrid",
             total_candidates=len(hits),
             degraded=bool(getattr(self.engine.plane.fabric,
                                   "degraded", False)))
+        if facet_domains is not None and counts is not None:
+            resp.total_matches = counts.total
+            resp.facets = self._facets_dict(counts)
+        return resp
 
     def fetch_page(self, url: str) -> Document | None:
         """Cache-first page fetch (reference: services.py:220-335);
