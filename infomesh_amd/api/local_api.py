@@ -76,18 +76,21 @@ def create_app(ctx: AppContext, api_key: str = "",
     def search(q: str, limit: int = 10, mode: str = "auto",
                include_domains: str = "", exclude_domains: str = "",
                recency_days: float = 0, facets: int = 0,
-               facet_domains: str = ""):
+               facet_domains: str = "", top_domains: int = 0):
         """include_domains / exclude_domains: comma-separated exact
         domains to allow / block; recency_days: crawled that recently.
         facets=1 adds "total_matches" and "facets" to the answer
         (AppContext.search says what they cover); facet_domains:
-        comma-separated domains to count."""
+        comma-separated domains to count; top_domains: with facets=1,
+        how many of the match set's top domains to add (at most 32)."""
         if not q.strip():
             raise HTTPException(400, "empty query")
         kw = {}
         if facets:
             kw = {"facets": True,
                   "facet_domains": [d for d in facet_domains.split(",") if d]}
+            if top_domains:
+                kw["top_domains"] = top_domains
         try:
             resp = ctx.search(
                 q, limit=min(limit, 50), mode=mode,

@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from .index.doc_attrs import (DocFilter, FacetCounts, FacetSpec, TermOps,
-                              facet_results, pack_attrs, pack_facets)
+                              domain_hash, facet_results, pack_attrs,
+                              pack_facets)
 from .index.gpu_index import CpuShard, GpuShard, bm25_term_ids
 from .index.local_store import (Document, LocalStore, SearchHit,
                                 extract_domain)
@@ -65,6 +66,9 @@ class HybridEngine:
         self._pending_texts: list[str] = []
         self._pending_ids: list[int] = []
         self._pending_attrs: list[tuple] = []
+        # 32-bit domain hash -> the first name seen with it, for the top
+        # domains of search_with_facets (which come back as hashes)
+        self._domain_names: dict[int, str] = {}
         # (embeddings and postings of already-built docs live in the
         # shard itself: flush merges rather than re-accumulating, so
         # engine memory does not grow with corpus size)
@@ -79,9 +83,22 @@ class HybridEngine:
         self._pending_texts.append(text[:self.embed_max_chars])
         self._pending_ids.append(doc.doc_id)
         # filter attributes (site:/lang:/after:/before: on the GPU plane)
+        domain = doc.domain or extract_domain(doc.url)
         self._pending_attrs.append(pack_attrs(
-            doc.language, doc.domain or extract_domain(doc.url),
-            doc.crawled_at or time.time()))
+            doc.language, domain, doc.crawled_at or time.time()))
+        self.note_domain(domain)
+
+    def note_domain(self, domain: str | None) -> None:
+        """Remember a stored domain's name under its hash; the first
+        name wins."""
+        name = (domain or "").strip().lower()
+        self._domain_names.setdefault(domain_hash(name), name)
+
+    def domain_name(self, h: int) -> str | None:
+        """The name of a domain hash that FacetCounts.top_domains
+        reports, None for one no add_document brought (a shard loaded
+        from a manifest)."""
+        return self._domain_names.get(int(h))
 
     def delete_documents(self, doc_ids) -> int:
         """Forget documents at once, with no flush: pending entries are
@@ -253,7 +270,9 @@ class HybridEngine:
         matches iff it passes the query's filter and operands, is not
         deleted, and holds at least one query term (FacetSpec says it in
         full). The hits are those of search_many; a query whose entry in
-        facets.domains is None (or missing) gets None."""
+        facets.domains is None (or missing) gets None. A row of
+        facets.top_domains adds the first T domains of the match set by
+        count (FacetCounts.top_domains, as hashes: domain_name)."""
         return self._search_many(queries, limit, use_dense, filters,
                                  require, exclude, facets)
 
@@ -308,7 +327,7 @@ class HybridEngine:
         counts: list[FacetCounts | None] = [None] * B
         if fused.facets is not None:
             counts = facet_results(facets, packed, fused.facets.cpu().numpy(),
-                                   n_rows=B)
+                                   n_rows=B, top=fused.top_domains)
         ids = fused.ids.tolist()
         scores = fused.scores.tolist()
         out: list[list[SearchHit]] = []

@@ -117,6 +117,11 @@ class TermOps:
 FACET_MAX_EDGES = 7     # date edges per batch      (ops/csrc/facets.hip)
 FACET_MAX_LANGS = 32    # listed languages per batch
 FACET_MAX_DOMS = 64     # domain hashes per row
+TOP_DOMAINS_MAX = 32    # top domains a row may ask for (T)
+# What every shard reports per top row: its first TOP_FETCH domains, and
+# one more entry whose count is the shard's cut-off (ops/csrc/domtop.hip
+# selects TOP_FETCH + 1; the query plane merges the reports).
+TOP_FETCH = 64
 
 
 def facet_slots(E: int, L: int) -> dict[str, int]:
@@ -145,10 +150,17 @@ class FacetSpec:
     languages: 2-letter codes, one list per batch. domains: one entry
     per row, a tuple of domain names to count or None for a row that is
     not counted. Domains count by their 32-bit hash (domain_hash), as
-    the filters compare them: two names with one hash share a count."""
+    the filters compare them: two names with one hash share a count.
+
+    top_domains: one T per row, 0 (or a missing entry) for none: the
+    first T domains of the row's whole match set by count descending,
+    then hash ascending as unsigned, whatever the caller listed. T is
+    at most TOP_DOMAINS_MAX, and a row with T > 0 is a counted row
+    (domains[i] is not None; () will do)."""
     date_edges: tuple[int, ...] = ()
     languages: tuple[str, ...] = ()
     domains: tuple[tuple[str, ...] | None, ...] = ()
+    top_domains: tuple[int, ...] = ()
 
 
 @dataclass(frozen=True)
@@ -158,7 +170,14 @@ class FacetCounts:
     <= crawled_at (len(edges) + 1 buckets); date_zero: crawled_at == 0.
     languages / domains: one count per name, in the caller's order.
     total == date_zero + sum(dates) == language_zero + language_other
-    + (the counts of the distinct listed languages)."""
+    + (the counts of the distinct listed languages).
+
+    top_domains: None unless the row asked for top domains, else its
+    (hash, count) pairs in order; every count is exact over all serving
+    shards. top_domains_exact: the pairs are the true first T. When it
+    is False a domain that is not shown may hold up to
+    top_domains_bound matches (the sum of the shards' cut-offs) and
+    belong among them."""
     total: int
     date_zero: int
     dates: tuple[int, ...]
@@ -166,6 +185,9 @@ class FacetCounts:
     language_zero: int
     language_other: int
     domains: dict
+    top_domains: tuple[tuple[int, int], ...] | None = None
+    top_domains_exact: bool = True
+    top_domains_bound: int = 0
 
 
 @dataclass(frozen=True)
@@ -173,13 +195,20 @@ class PackedFacets:
     """A FacetSpec as the kernel reads it (and as the query plane
     forwards it between ranks): edges and language codes ascending and
     unique, `rows` the counted batch rows, `lists` each one's domain
-    hashes, unique and ascending as unsigned."""
+    hashes, unique and ascending as unsigned. top: one T per counted
+    row (0: no top domains), or () when no row asked."""
     edges: tuple[int, ...]
     langs: tuple[int, ...]
     rows: tuple[int, ...]
     lists: tuple[tuple[int, ...], ...]
+    top: tuple[int, ...] = ()
 
     def __post_init__(self):
+        if any(t < 0 or t > TOP_DOMAINS_MAX for t in self.top):
+            raise ValueError(
+                f"facets: top domains {max(self.top)} / {min(self.top)}; "
+                f"0 <= T <= {TOP_DOMAINS_MAX}")
+        assert len(self.top) in (0, len(self.rows))
         widest = max((len(h) for h in self.lists), default=0)
         if len(self.edges) > FACET_MAX_EDGES \
                 or len(self.langs) > FACET_MAX_LANGS \
@@ -194,6 +223,11 @@ class PackedFacets:
     def width(self) -> int:
         return facet_width(len(self.edges), len(self.langs),
                            max((len(h) for h in self.lists), default=0))
+
+    @property
+    def top_rows(self) -> tuple[int, ...]:
+        """The batch rows that asked for top domains, in `rows` order."""
+        return tuple(b for b, t in zip(self.rows, self.top) if t > 0)
 
     def tables(self):
         """(rows [R], edges [E], langs [L], dom_desc [R, 2], doms) as
@@ -221,21 +255,44 @@ def pack_facets(spec, B: int) -> PackedFacets | None:
     codes = [lang16(c) for c in spec.languages]
     if 0 in codes:
         raise ValueError("facets: languages are 2-letter ASCII codes")
+    if len(spec.top_domains) > B:
+        raise ValueError("facets: more top-domain entries than rows")
+    tops = {i: int(t) for i, t in enumerate(spec.top_domains) if t}
+    for i, t in tops.items():
+        if t < 0 or t > TOP_DOMAINS_MAX:
+            raise ValueError(
+                f"facets: row {i} asks for {t} top domains; "
+                f"0 <= T <= {TOP_DOMAINS_MAX}")
+        if i >= len(spec.domains) or spec.domains[i] is None:
+            raise ValueError(
+                f"facets: row {i} asks for top domains but is not a "
+                f"counted row (domains[{i}] is None)")
     rows = tuple(i for i, d in enumerate(spec.domains) if d is not None)
     if not rows:
         return None
     return PackedFacets(
         edges=tuple(sorted({_clamp_u32(e) for e in spec.date_edges})),
         langs=tuple(sorted(set(codes))), rows=rows,
-        lists=tuple(_hash_list(spec.domains[i]) for i in rows))
+        lists=tuple(_hash_list(spec.domains[i]) for i in rows),
+        top=tuple(tops.get(i, 0) for i in rows) if tops else ())
 
 
 def facet_results(spec: FacetSpec, packed: PackedFacets | None,
-                  counts, n_rows: int | None = None
+                  counts, n_rows: int | None = None, top=None
                   ) -> list[FacetCounts | None]:
     """counts [R, F] (the rows of `packed`, any integer array-like) ->
     one FacetCounts or None per batch row, in the caller's names and
-    order: the permutation back from pack_facets' sorting."""
+    order: the permutation back from pack_facets' sorting. top: None, or
+    one (pairs, exact, bound) per row of packed.top_rows, as the query
+    plane merges them; each is cut to the row's T here."""
+    tops = {}
+    if packed is not None and top is not None:
+        t_of = dict(zip(packed.rows, packed.top))
+        for b, (pairs, exact, bound) in zip(packed.top_rows, top):
+            tops[b] = dict(
+                top_domains=tuple((int(h), int(c))
+                                  for h, c in pairs[:t_of[b]]),
+                top_domains_exact=bool(exact), top_domains_bound=int(bound))
     n = len(spec.domains) if n_rows is None else n_rows
     out: list[FacetCounts | None] = [None] * n
     if packed is None:
@@ -258,8 +315,38 @@ def facet_results(spec: FacetSpec, packed: PackedFacets | None,
             language_zero=int(c[r, sl["lang_zero"]]),
             language_other=int(c[r, sl["lang_other"]]),
             domains={name: int(c[r, sl["dom0"] + dom_at[domain_hash(name)]])
-                     for name in spec.domains[b]})
+                     for name in spec.domains[b]},
+            **tops.get(b, {}))
     return out
+
+
+def domain_tables_np(attrs: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """(dom_keys [D], dom_id [N]) of attrs [N, 4], as int32: the distinct
+    w2 words ascending as unsigned (their u32 bits), and every row's index
+    into them. The tables a shard keeps per epoch for domain_count."""
+    a = np.ascontiguousarray(attrs).view(np.uint32).reshape(-1, 4)
+    keys, inv = np.unique(a[:, 2], return_inverse=True)
+    return keys.view(np.int32), inv.reshape(-1).astype(np.int32)
+
+
+def domain_top_np(scores: np.ndarray, fail: np.ndarray | None,
+                  attrs: np.ndarray, rows, K: int) -> np.ndarray:
+    """The oracle of top domains: scores [B, N], fail bool [B, N] or
+    None, attrs [N, 4], rows the batch rows to count -> [R, K, 2] int32
+    of (hash bits, count) pairs: per row the first K domains (w2 words)
+    of the matching documents (FacetSpec's rule) by count descending,
+    then hash ascending as unsigned; (0, 0) past the last one."""
+    a = np.ascontiguousarray(attrs).view(np.uint32).reshape(-1, 4)
+    out = np.zeros((len(rows), K, 2), dtype=np.int64)
+    for r, b in enumerate(rows):
+        m = scores[b] > 0
+        if fail is not None:
+            m = m & ~fail[b]
+        keys, cnt = np.unique(a[m, 2], return_counts=True)
+        order = np.lexsort((keys, -cnt.astype(np.int64)))[:K]
+        out[r, :len(order), 0] = keys[order]
+        out[r, :len(order), 1] = cnt[order]
+    return out.astype(np.uint32).view(np.int32)
 
 
 def facet_counts_np(scores: np.ndarray, fail: np.ndarray | None,

@@ -33,7 +33,8 @@ import numpy as np
 import torch
 
 from ..hashing import hash64
-from .doc_attrs import (DEAD_BIT, DocFilter, FacetSpec, TermOps,
+from .doc_attrs import (DEAD_BIT, TOP_FETCH, U32_MAX, DocFilter, FacetSpec,
+                        TermOps, domain_tables_np, domain_top_np,
                         facet_counts_np, pack_facets, pack_pred,
                         pack_pred_sets, passes, words_i32)
 
@@ -85,6 +86,26 @@ def bm25_term_ids(text: str, vocab: int = BM25_VOCAB) -> np.ndarray:
 
 
 @dataclass
+class DomainTally:
+    """A shard's per-domain match counts of one batch's top rows, kept
+    for the query plane's second round: cnt [Rt, D] i32 over the shard's
+    domain ids, dom_keys [D] i32, the ids' hashes (u32 bits, ascending
+    as unsigned). cnt may be the shard's workspace: it holds until the
+    shard's next batch."""
+    cnt: torch.Tensor
+    dom_keys: torch.Tensor
+
+    def lookup(self, hashes: torch.Tensor) -> torch.Tensor:
+        """hashes [Rt, U] (u32 bits, any integer dtype) -> [Rt, U] i32:
+        row r's count of every hash, 0 for one the shard does not hold."""
+        keys = self.dom_keys.long() & U32_MAX
+        h = hashes.to(keys.device).long() & U32_MAX
+        pos = torch.searchsorted(keys, h).clamp(max=keys.numel() - 1)
+        got = self.cnt.gather(1, pos)
+        return torch.where(keys[pos] == h, got, torch.zeros_like(got))
+
+
+@dataclass
 class ShardHits:
     """Fixed-size per-shard top-k results (scores + GLOBAL doc ids)."""
     bm25_scores: torch.Tensor   # [B, k] f32
@@ -94,6 +115,12 @@ class ShardHits:
     # [R, F] i32 facet counts of the rows a FacetSpec names (layout:
     # ops/csrc/facets.hip); None when the caller asked for none
     facets: torch.Tensor | None = None
+    # [Rt, TOP_FETCH + 1, 2] i32 (hash bits, count) pairs: the shard's
+    # first domains of every row that asked for top domains, in order
+    # (ops/csrc/domtop.hip), and the tally they were selected from; None
+    # when no row asked
+    dom_top: torch.Tensor | None = None
+    dom_tally: DomainTally | None = None
 
 
 @dataclass
@@ -137,6 +164,11 @@ class GpuShard:
         self._attr_buf: torch.Tensor | None = None  # [cap, 4] i32
         self.n_dead = 0
         self._live_bits = None   # cached live-only mask (+ ready event)
+        # per-epoch domain tables (dom_keys [D], dom_id [N]), built by
+        # the first request for top domains, and the [R, D] count
+        # workspace of ops/csrc/domtop.hip
+        self._dom_tables = None
+        self._dom_ws: torch.Tensor | None = None
         self._topk = None
         self._topk_dense = None
         self._topk_pruned = None    # dense selector over block maxima
@@ -465,6 +497,10 @@ class GpuShard:
         self._dense_bmax = {}
         self._bm25_hists = {}
         self._live_bits = None
+        # n_docs or the row order changed (a delete alone sets a dead
+        # bit and keeps them)
+        self._dom_tables = None
+        self._dom_ws = None
 
     def optimize(self) -> None:
         """Merge all posting segments into one, entirely on-device:
@@ -704,10 +740,30 @@ class GpuShard:
 
     def hbm_bytes(self) -> int:
         total = sum(s.hbm_bytes() for s in self.segments)
-        for t in (self._emb_buf, self._gid_buf, self._attr_buf):
+        for t in (self._emb_buf, self._gid_buf, self._attr_buf,
+                  self._dom_ws, *(self._dom_tables or ())):
             if t is not None:
                 total += t.numel() * t.element_size()
         return total
+
+    def _domain_tables(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """(dom_keys [D] i32, dom_id [N] i32) of this epoch: the distinct
+        w2 words of the shard's rows, ascending as unsigned, and every
+        row's index into them. Built on the device on first use."""
+        if self._dom_tables is None:
+            w2 = self.attrs[:, 2].long() & U32_MAX
+            keys, inv = torch.unique(w2, return_inverse=True)
+            keys = torch.where(keys > 0x7FFFFFFF, keys - (1 << 32), keys)
+            self._dom_tables = (keys.to(torch.int32).contiguous(),
+                                inv.to(torch.int32).contiguous())
+        return self._dom_tables
+
+    def _domain_ws(self, R: int, D: int) -> torch.Tensor:
+        """[R, D] i32 view of the count workspace, grown on demand."""
+        if self._dom_ws is None or self._dom_ws.numel() < R * D:
+            self._dom_ws = torch.empty(R * D, device=self.device,
+                                       dtype=torch.int32)
+        return self._dom_ws[:R * D].view(R, D)
 
     # ----------------------------------------------------------- search
     def _get_topk(self):
@@ -823,6 +879,16 @@ class GpuShard:
         return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
                                 _mask, term_ops, None)[:2]
 
+    def search_bm25_top(self, queries_terms: list[np.ndarray], k: int,
+                        facets, scores_buf: torch.Tensor | None = None,
+                        mark=None, filters=None, _mask=None, term_ops=None):
+        """search_bm25_facets plus the top domains of the rows that ask
+        for them: -> (values, indices, counts, dom_top, dom_tally), the
+        last two as ShardHits holds them (None when no row asks)."""
+        return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
+                                _mask, term_ops,
+                                pack_facets(facets, len(queries_terms)))
+
     def search_bm25_facets(self, queries_terms: list[np.ndarray], k: int,
                            facets, scores_buf: torch.Tensor | None = None,
                            mark=None, filters=None, _mask=None,
@@ -839,7 +905,7 @@ class GpuShard:
         pass-1 histogram."""
         return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
                                 _mask, term_ops,
-                                pack_facets(facets, len(queries_terms)))
+                                pack_facets(facets, len(queries_terms)))[:3]
 
     def _bm25_plane(self, queries_terms, k, scores_buf, mark, filters,
                     _mask, term_ops, facets):
@@ -914,13 +980,28 @@ class GpuShard:
                 doms_t, mask=None if mask is None else mask[0],
                 row_pred=None if mask is None else mask[1])
             tp = mark("shard.facets", tp)
+        dom_top = tally = None
+        if facets is not None and facets.top_rows:
+            # the same scores and the same mask once more, 4 bytes per
+            # match: the tally by domain id, then its first entries
+            dom_keys, dom_id = self._domain_tables()
+            top_rows = torch.tensor(facets.top_rows, dtype=torch.int32)
+            D = dom_keys.numel()
+            cnt = K.domain_count(
+                scores, top_rows, dom_id, D,
+                mask=None if mask is None else mask[0],
+                row_pred=None if mask is None else mask[1],
+                out=self._domain_ws(len(facets.top_rows), D))
+            dom_top = K.domain_select(cnt, dom_keys, TOP_FETCH + 1)
+            tally = DomainTally(cnt, dom_keys)
+            tp = mark("shard.topdomains", tp)
         if mask is None:
             out = topk(scores, k, ext_hist1=hist)
         else:
             out = topk(scores, k, mask=mask[0], row_pred=mask[1])
         mark("shard.bm25topk", tp)
         self._bm25_scores_buf = scores
-        return out[0], out[1], counts
+        return out[0], out[1], counts, dom_top, tally
 
     def search(self, queries_terms: list[np.ndarray],
                query_emb: torch.Tensor | None, k: int = 100,
@@ -958,13 +1039,13 @@ class GpuShard:
         k = min(k, N)
         tp = _time.perf_counter()
         mask = self._mask_for(filters, B, term_ops)   # once for both planes
-        counts = None
+        counts = dom_top = tally = None
         if facets is None:
             bm_vals, bm_idx = self.search_bm25(queries_terms, k,
                                                scores_buf=scores_buf,
                                                mark=mark, _mask=mask)
         else:
-            bm_vals, bm_idx, counts = self.search_bm25_facets(
+            bm_vals, bm_idx, counts, dom_top, tally = self.search_bm25_top(
                 queries_terms, k, facets, scores_buf=scores_buf, mark=mark,
                 _mask=mask)
         tp = _time.perf_counter()
@@ -980,7 +1061,8 @@ class GpuShard:
         return ShardHits(bm25_scores=bm_vals,
                          bm25_ids=self.to_global(bm_idx),
                          dense_scores=dn_vals,
-                         dense_ids=self.to_global(dn_idx), facets=counts)
+                         dense_ids=self.to_global(dn_idx), facets=counts,
+                         dom_top=dom_top, dom_tally=tally)
 
     def search_dense(self, query_emb: torch.Tensor, k: int,
                      mark=None, filters=None, _mask=None, term_ops=None
@@ -1191,12 +1273,26 @@ class CpuShard(GpuShard):
         st = torch.from_numpy(scores)
         fail = self._fail_rows(filters, B, term_ops)
         bm_vals, bm_idx = self._masked_topk(st, fail, k)
-        counts = None
+        counts = dom_top = tally = None
         packed = pack_facets(facets, B)
         if packed is not None:
+            fail_np = None if fail is None else fail.numpy()
             counts = torch.from_numpy(facet_counts_np(
-                scores, None if fail is None else fail.numpy(),
-                self.attrs.numpy(), packed))
+                scores, fail_np, self.attrs.numpy(), packed))
+            if packed.top_rows:
+                dom_top = torch.from_numpy(domain_top_np(
+                    scores, fail_np, self.attrs.numpy(), packed.top_rows,
+                    TOP_FETCH + 1))
+                dom_keys, dom_id = self._domain_tables()
+                D = dom_keys.numel()
+                cnt = self._domain_ws(len(packed.top_rows), D)
+                for r, b in enumerate(packed.top_rows):
+                    m = scores[b] > 0
+                    if fail_np is not None:
+                        m &= ~fail_np[b]
+                    cnt[r] = torch.from_numpy(np.bincount(
+                        dom_id.numpy()[m], minlength=D).astype(np.int32))
+                tally = DomainTally(cnt, dom_keys)
         if query_emb is not None and self.embeddings is not None:
             d_scores = query_emb.float().cpu() @ self.embeddings.float().T
             dn_vals, dn_idx = self._masked_topk(d_scores, fail, k)
@@ -1211,4 +1307,13 @@ class CpuShard(GpuShard):
 
         return ShardHits(bm25_scores=bm_vals, bm25_ids=to_global(bm_idx),
                          dense_scores=dn_vals.float(),
-                         dense_ids=to_global(dn_idx), facets=counts)
+                         dense_ids=to_global(dn_idx), facets=counts,
+                         dom_top=dom_top, dom_tally=tally)
+
+    def _domain_tables(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """GpuShard's tables, built with numpy."""
+        if self._dom_tables is None:
+            self._dom_tables = tuple(
+                torch.from_numpy(t)
+                for t in domain_tables_np(self.attrs.numpy()))
+        return self._dom_tables

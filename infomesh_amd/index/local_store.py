@@ -325,6 +325,11 @@ class LocalStore:
                 + " OR ".join(where), params))
         return sorted(found)
 
+    def all_domains(self) -> list[str]:
+        """Every distinct stored domain, sorted."""
+        return sorted(r["domain"] for r in self.conn.execute(
+            "SELECT DISTINCT domain FROM documents") if r["domain"])
+
     def suggest(self, prefix: str, limit: int = 5) -> list[str]:
         """Title-prefix suggestions (reference: local_store.py:354).
 

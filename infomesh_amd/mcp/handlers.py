@@ -43,10 +43,12 @@ class Handlers:
                    fetch_full_content: bool = False,
                    validate: bool = False, facets: bool = False,
                    facet_domains: list[str] | None = None,
+                   top_domains: int = 0,
                    **_) -> dict[str, Any]:
         """facets: add "total_matches" and "facets" (counts over every
         matching document when the engine serves the query, see
-        AppContext.search); facet_domains: exact domains to count. Both
+        AppContext.search); facet_domains: exact domains to count;
+        top_domains: how many of the match set's top domains to add. Both
         fields are null when the domain lists went over the cap and the
         hits were filtered after an unfiltered search."""
         if not query or not query.strip():
@@ -81,6 +83,8 @@ class Handlers:
         # the store expands each name to the exact domains it holds.
         fkw = {"facets": True, "facet_domains": list(facet_domains or ())} \
             if facets else {}
+        if facets and top_domains:
+            fkw["top_domains"] = int(top_domains)
         include = exclude = None
         if domain_allowlist:
             # nothing stored under an allowed name: keep the names, which

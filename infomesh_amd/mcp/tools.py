@@ -37,6 +37,10 @@ TOOLS: list[dict] = [
                 "facet_domains": {"type": "array",
                                   "items": {"type": "string"},
                                   "description": "exact domains to count"},
+                "top_domains": {"type": "integer",
+                                "description": "with facets: how many of "
+                                               "the match set's top "
+                                               "domains to add (<= 32)"},
                 "explain": {"type": "boolean"},
                 "chunk_size": {"type": "integer"},
                 "answer_mode": {

@@ -118,14 +118,26 @@ _SIGNATURES: dict[str, list] = {
     "infomesh_facet_chunk_docs": [],
     "infomesh_facet_width": [c_int, c_int, c_int],
     "infomesh_facet_slot": [c_int, c_int, c_int],
+    "infomesh_domain_count": [c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_int, c_int, c_long,
+                              c_long, c_int, c_int, c_void_p],
+    "infomesh_domain_select": [c_void_p, c_void_p, c_void_p, c_int, c_int,
+                               c_int, c_void_p],
+    "infomesh_domtop_chunk_docs": [],
+    "infomesh_domtop_lds_slots": [],
+    "infomesh_domtop_k_max": [],
 }
 
 # Everything not listed here returns void. topk_*_u32: lengths;
 # dense_scores, gemm_bf16_nt_bmax: dispatch eligibility (0 = launched);
 # gemm_tile: tile code; gemm_bmax_width: columns per block maximum;
 # term_block_docs: documents per workgroup of term_bitmask; facet_*: the
-# chunk size and the slot layout of facet_counts.
+# chunk size and the slot layout of facet_counts; domtop_*: the chunk
+# size, the LDS table size and the K cap of csrc/domtop.hip.
 _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
+             "infomesh_domtop_chunk_docs": c_int,
+             "infomesh_domtop_lds_slots": c_int,
+             "infomesh_domtop_k_max": c_int,
              "infomesh_facet_chunk_docs": c_int,
              "infomesh_facet_width": c_int,
              "infomesh_facet_slot": c_int,

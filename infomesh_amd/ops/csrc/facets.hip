@@ -59,9 +59,10 @@
 // with ~4 % of its lanes, each time behind a dependent attribute load.
 // docs/performance.md has the figures of both.
 #include "common.h"
+#include "match_queue.h"
 
-#define FACET_THREADS 256
-#define FACET_CHUNK 8192   // documents per workgroup: 8 steps of 1024
+#define FACET_THREADS MATCHQ_THREADS
+#define FACET_CHUNK MATCHQ_CHUNK   // documents per workgroup
 #define FACET_MAX_EDGES 7
 #define FACET_MAX_LANGS 32
 #define FACET_MAX_DOMS 64
@@ -73,8 +74,6 @@
 #define FACET_COPIES 8
 #define FACET_STRIDE 136
 static_assert(FACET_STRIDE >= FACET_F_MAX, "a copy holds every slot");
-static_assert(FACET_CHUNK <= 65536 && FACET_CHUNK % (FACET_THREADS * 4) == 0,
-              "the queue holds chunk-local u16 document numbers");
 
 #define FACET_TOTAL 0
 #define FACET_DATE_ZERO 1
@@ -149,55 +148,9 @@ __global__ __launch_bounds__(FACET_THREADS) void facet_counts_kernel(
   const long c0 = (long)blockIdx.y * FACET_CHUNK;
   const long c1 = min(c0 + FACET_CHUNK, N);
   const float* row = scores + (long)b * N;
-  const unsigned long long below = (1ull << (tid & (WAVE - 1))) - 1ull;
-  // Step 1, the streaming read: queue the chunk's matching documents.
-  // The trip count is block-uniform, so every lane reaches the ballots.
-  for (long base = c0; base < c1; base += FACET_THREADS * 4) {
-    const long d = base + tid * 4;
-    unsigned m = 0;  // bit j: document d + j matches
-    if (d < c1) {    // c1 <= N and d is a multiple of 4
-      // bit j: document d + j exists (and passes)
-      unsigned ok = d + 4 <= N ? 15u : (1u << (unsigned)(N - d)) - 1u;
-      if constexpr (MASKED) ok &= mrow[d >> 5] >> (unsigned)(d & 31);
-      if (ok) {
-        if (d + 4 <= N) {
-          // row = scores + b * N: with N % 4 != 0 and b > 0 this address
-          // is 4-byte aligned only. It relies on the unaligned global
-          // dwordx4 loads gfx950 does in hardware, as topk.hip's float4
-          // reads of a row do; the tail branch is about the row's END
-          // (fewer than four documents left), not about alignment.
-          const float4 v = *reinterpret_cast<const float4*>(row + d);
-          m = (v.x > 0.0f ? 1u : 0u) | (v.y > 0.0f ? 2u : 0u) |
-              (v.z > 0.0f ? 4u : 0u) | (v.w > 0.0f ? 8u : 0u);
-        } else {
-          for (int j = 0; j < 3; ++j)
-            if (d + j < N && row[d + j] > 0.0f) m |= 1u << j;
-        }
-        m &= ok;
-      }
-    }
-    // one queue reservation per wave: ballots and popcounts place every
-    // lane's matches, a single LDS atomic moves the tail
-    const unsigned long long b0 = __ballot(m & 1u), b1 = __ballot(m & 2u);
-    const unsigned long long b2 = __ballot(m & 4u), b3 = __ballot(m & 8u);
-    const unsigned n0 = __popcll(b0), n1 = __popcll(b1), n2 = __popcll(b2);
-    const unsigned nw = n0 + n1 + n2 + __popcll(b3);  // wave-uniform
-    if (nw) {
-      unsigned at = 0;
-      if ((tid & (WAVE - 1)) == 0) at = atomicAdd(&s_n, nw);
-      at = __shfl(at, 0, WAVE);
-      // a document is queued at most once, so the tail never passes
-      // FACET_CHUNK; d - c0 < FACET_CHUNK <= 65536
-      const unsigned loc = (unsigned)(d - c0);
-      if (m & 1u) s_q[at + __popcll(b0 & below)] = (unsigned short)loc;
-      at += n0;
-      if (m & 2u) s_q[at + __popcll(b1 & below)] = (unsigned short)(loc + 1);
-      at += n1;
-      if (m & 4u) s_q[at + __popcll(b2 & below)] = (unsigned short)(loc + 2);
-      at += n2;
-      if (m & 8u) s_q[at + __popcll(b3 & below)] = (unsigned short)(loc + 3);
-    }
-  }
+  // Step 1, the streaming read: queue the chunk's matching documents
+  // (match_queue.h; domtop.hip starts the same way).
+  match_queue_fill<MASKED>(row, mrow, c0, c1, N, s_q, &s_n);
   __syncthreads();
   // Step 2: one queued document per lane, so the attribute loads of 256
   // matches are in flight together whatever the score density.

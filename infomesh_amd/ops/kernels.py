@@ -683,6 +683,97 @@ def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
     return counts
 
 
+def domtop_chunk_docs() -> int:
+    """Documents per workgroup of domain_count (DOMTOP_CHUNK)."""
+    return int(_ext.lib().infomesh_domtop_chunk_docs())
+
+
+def domtop_lds_slots() -> int:
+    """Slots of domain_count's per-workgroup LDS table."""
+    return int(_ext.lib().infomesh_domtop_lds_slots())
+
+
+def domtop_k_max() -> int:
+    """The largest K domain_select takes."""
+    return int(_ext.lib().infomesh_domtop_k_max())
+
+
+def domain_count(scores: torch.Tensor, rows: torch.Tensor,
+                 dom_id: torch.Tensor, D: int,
+                 mask: torch.Tensor | None = None,
+                 row_pred: torch.Tensor | None = None,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """Matching documents per domain id (csrc/domtop.hip; the match rule
+    is the one of facet_counts): scores [B, N] f32, dom_id [N] i32 with
+    every entry in [0, D) and, with a mask, mask [P, W] i32 + row_pred
+    [B] i32, on the device. rows [R] i32 names the batch rows to count
+    and is checked here, on the host, before the kernel indexes with it
+    (a host tensor is uploaded, a device tensor copied back). out: a
+    contiguous [R, D] i32 device tensor to count into; it is zeroed
+    here. Returns cnt [R, D] i32. dom_id is the caller's to keep inside
+    [0, D): the kernel drops an id outside it."""
+    _check(scores, torch.float32, "scores")
+    _check(dom_id, torch.int32, "dom_id")
+    assert scores.dim() == 2
+    B, N = scores.shape
+    if D < 1:
+        raise ValueError(f"domain_count: D = {D}; at least one domain")
+    assert N >= 1 and dom_id.shape == (N,), "dom_id: [N]"
+    assert (mask is None) == (row_pred is None), \
+        "mask and row_pred go together"
+    W = P = 0
+    if mask is not None:
+        _check(mask, torch.int32, "mask")
+        _check(row_pred, torch.int32, "row_pred")
+        assert mask.dim() == 2 and mask.shape[1] * 32 >= N
+        assert row_pred.numel() == B
+        P, W = mask.shape
+    h_rows = _host_words(rows, "rows")
+    assert h_rows.dim() == 1 and h_rows.numel() >= 1, "rows: [R], R >= 1"
+    R = h_rows.numel()
+    assert bool(((h_rows >= 0) & (h_rows < B)).all()), \
+        "rows points outside the batch"
+    assert (N + domtop_chunk_docs() - 1) // domtop_chunk_docs() <= 65535
+    dev = scores.device
+    rows_d = rows if rows.is_cuda else rows.to(dev, non_blocking=True)
+    if out is None:
+        out = torch.zeros((R, D), device=dev, dtype=torch.int32)
+    else:
+        _check(out, torch.int32, "out")
+        assert out.shape == (R, D), "out: [R, D]"
+        out.zero_()
+    _ext.lib().infomesh_domain_count(
+        scores.data_ptr(), rows_d.data_ptr(), _ptr(mask), _ptr(row_pred),
+        dom_id.data_ptr(), out.data_ptr(), B, R, N, W, P, D,
+        _ext.stream_ptr())
+    return out
+
+
+def domain_select(cnt: torch.Tensor, dom_keys: torch.Tensor,
+                  K: int) -> torch.Tensor:
+    """The first K domains of every row of cnt [R, D] i32 (counts >= 0)
+    by count descending, then id ascending (csrc/domtop.hip), as
+    (dom_keys[id], count) pairs: [R, K, 2] i32. count > 0 marks a real
+    entry; past the last one the pairs are (0, 0). dom_keys [D] i32. K
+    outside 1 .. domtop_k_max() is a ValueError, and nothing is
+    launched."""
+    _check(cnt, torch.int32, "cnt")
+    _check(dom_keys, torch.int32, "dom_keys")
+    assert cnt.dim() == 2
+    R, D = cnt.shape
+    if not 1 <= K <= domtop_k_max():
+        raise ValueError(
+            f"domain_select: K = {K}; 1 <= K <= {domtop_k_max()}")
+    if D < 1:
+        raise ValueError(f"domain_select: D = {D}; at least one domain")
+    assert R >= 1 and dom_keys.shape == (D,), "dom_keys: [D]"
+    out = torch.empty((R, K, 2), device=cnt.device, dtype=torch.int32)
+    _ext.lib().infomesh_domain_select(
+        cnt.data_ptr(), dom_keys.data_ptr(), out.data_ptr(), R, D, K,
+        _ext.stream_ptr())
+    return out
+
+
 def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
                qt_off: torch.Tensor, qt_ut: torch.Tensor,
                qt_idf: torch.Tensor, u_begin: torch.Tensor,

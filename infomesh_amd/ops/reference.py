@@ -245,14 +245,76 @@ def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
         rows=tuple(int(b) for b in rows.cpu().numpy()),
         lists=tuple(tuple(int(v) for v in h[off:off + n])
                     for off, n in desc))
-    fail = None
-    if mask is not None:
-        words = mask.cpu().numpy().view(np.uint32)
-        ok = np.unpackbits(words.view(np.uint8), axis=1,
-                           bitorder="little")[:, :N].astype(bool)
-        fail = ~ok[row_pred.cpu().numpy().astype(np.int64)]
-    return torch.from_numpy(facet_counts_np(s, fail, attrs.cpu().numpy(),
-                                            packed))
+    return torch.from_numpy(facet_counts_np(
+        s, _fail_rows(mask, row_pred, N), attrs.cpu().numpy(), packed))
+
+
+def _fail_rows(mask, row_pred, N: int):
+    """bool [B, N], True where a document fails its row's mask; None
+    without a mask."""
+    import numpy as np
+    if mask is None:
+        return None
+    words = mask.cpu().numpy().view(np.uint32)
+    ok = np.unpackbits(words.view(np.uint8), axis=1,
+                       bitorder="little")[:, :N].astype(bool)
+    return ~ok[row_pred.cpu().numpy().astype(np.int64)]
+
+
+def domain_count(scores: torch.Tensor, rows: torch.Tensor,
+                 dom_id: torch.Tensor, D: int,
+                 mask: torch.Tensor | None = None,
+                 row_pred: torch.Tensor | None = None,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """Oracle of csrc/domtop.hip's domain_count, same arguments as
+    kernels.domain_count: cnt[r, i] = the matching documents of batch
+    row rows[r] (facet_counts' rule) whose dom_id is i. [R, D] i32."""
+    import numpy as np
+    s = scores.detach().float().cpu().numpy()
+    fail = _fail_rows(mask, row_pred, s.shape[1])
+    ids = dom_id.cpu().numpy().astype(np.int64)
+    cnt = np.zeros((rows.numel(), D), dtype=np.int64)
+    for r, b in enumerate(rows.cpu().numpy()):
+        m = s[b] > 0
+        if fail is not None:
+            m &= ~fail[b]
+        cnt[r] = np.bincount(ids[m], minlength=D)
+    return torch.from_numpy(cnt.astype(np.int32))
+
+
+def domain_select(cnt: torch.Tensor, dom_keys: torch.Tensor,
+                  K: int) -> torch.Tensor:
+    """Oracle of csrc/domtop.hip's domain_select, same arguments as
+    kernels.domain_select: per row the non-zero counts by count
+    descending, then hash ascending as unsigned (np.lexsort, as
+    index/doc_attrs.domain_top_np orders them), the first K as (hash
+    bits, count) pairs, (0, 0) behind them. [R, K, 2] i32."""
+    import numpy as np
+    c = cnt.cpu().numpy().astype(np.int64)
+    keys = dom_keys.cpu().numpy().view(np.uint32).astype(np.int64)
+    R, D = c.shape
+    out = np.zeros((R, K, 2), dtype=np.int64)
+    for r in range(R):
+        nz = np.nonzero(c[r])[0]
+        order = nz[np.lexsort((keys[nz], -c[r, nz]))][:K]
+        out[r, :len(order), 0] = keys[order]
+        out[r, :len(order), 1] = c[r, order]
+    return torch.from_numpy(out.astype(np.uint32).view(np.int32))
+
+
+def domain_top(scores: torch.Tensor, rows: torch.Tensor,
+               attrs: torch.Tensor, K: int,
+               mask: torch.Tensor | None = None,
+               row_pred: torch.Tensor | None = None) -> torch.Tensor:
+    """Oracle of domain_count followed by domain_select over a shard's
+    attribute records, with the kernels' arguments: the rules are
+    written once, in index/doc_attrs.domain_top_np, which CpuShard uses
+    as well; this function only unpacks the mask for it. [R, K, 2] i32."""
+    from ..index.doc_attrs import domain_top_np
+    s = scores.detach().float().cpu().numpy()
+    return torch.from_numpy(domain_top_np(
+        s, _fail_rows(mask, row_pred, s.shape[1]), attrs.cpu().numpy(),
+        [int(b) for b in rows.cpu().numpy()], K))
 
 
 def masked_topk(scores: torch.Tensor, k: int, bits: torch.Tensor,

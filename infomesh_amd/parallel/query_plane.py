@@ -18,8 +18,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ..index.doc_attrs import (HAS_ALLOW_BIT, HAS_BLOCK_BIT, U32_MAX,
-                               FacetSpec, PackedFacets, TermOps,
+from ..index.doc_attrs import (HAS_ALLOW_BIT, HAS_BLOCK_BIT, TOP_FETCH,
+                               U32_MAX, FacetSpec, PackedFacets, TermOps,
                                pack_facets, pack_pred_sets)
 from ..index.gpu_index import GpuShard, ShardHits
 from .fabric import Fabric
@@ -40,6 +40,9 @@ _HAS_LISTS = HAS_ALLOW_BIT | HAS_BLOCK_BIT
 # stripped before the predicates are unpacked, and only such a batch is
 # followed by the two broadcasts of _broadcast_facets.
 _HAS_FACETS = 1 << 20
+# Bit 40 of the hash count in _broadcast_facets' header: the spec asks
+# for top domains somewhere, and its body carries one T per counted row.
+_HAS_TOP = 1 << 40
 # Term operands (TermOps) ride in the same broadcast, as flag bits on the
 # row's term entries; term ids are below 2^17, so bits 40.. are free. A
 # require operand is its scoring term with bit 40 set, an exclude operand
@@ -105,6 +108,62 @@ class FusedHits:
     # FacetSpec names (doc_attrs.facet_results maps them back); None
     # when the batch had no spec
     facets: torch.Tensor | None = None
+    # one (pairs, exact, bound) per row that asked for top domains, in
+    # PackedFacets.top_rows order (rank_top_domains says what they are);
+    # None when no row asked
+    top_domains: list | None = None
+
+
+def gather_top_domains(reports: torch.Tensor, lookup, all_gather):
+    """Round 2 of the top domains, on every rank alike. reports
+    [W, Rt, TOP_FETCH + 1, 2] i32: every serving shard's first domains
+    per row as (hash bits, count) pairs in the contract's order (count
+    descending, then hash ascending as unsigned), the last entry being
+    the shard's cut-off: no domain it left unreported has a larger local
+    count there; 0 when it reported everything. lookup: this shard's
+    DomainTally.lookup; all_gather: the fabric's.
+
+    Every rank forms per row the sorted union of the reported hashes,
+    padded with 2^32 to the fixed width W * TOP_FETCH (all ranks hold
+    the same reports, hence the same union), looks up its own counts of
+    them, and the gathered lookups are summed: the exact global count of
+    every domain in the union. -> (union [Rt, U] i64, total [Rt, U]
+    i64, cut [Rt] i64, the sum of the cut-offs)."""
+    W, Rt = reports.shape[:2]
+    F = TOP_FETCH
+    h = reports[:, :, :F, 0].long() & U32_MAX
+    pad = U32_MAX + 1                       # sorts behind every hash
+    h = torch.where(reports[:, :, :F, 1] > 0, h, torch.full_like(h, pad))
+    h = h.permute(1, 0, 2).reshape(Rt, W * F).sort(dim=1).values
+    dup = torch.zeros_like(h, dtype=torch.bool)
+    dup[:, 1:] = h[:, 1:] == h[:, :-1]
+    union = torch.where(dup, torch.full_like(h, pad), h).sort(dim=1).values
+    mine = lookup((union & U32_MAX).to(torch.int32)).to(reports.device)
+    mine = torch.where(union < pad, mine, torch.zeros_like(mine))
+    total = all_gather(mine.contiguous()).long().sum(0)
+    return union, total, reports[:, :, F, 1].long().sum(0)
+
+
+def rank_top_domains(union, total, cut, W: int, tops) -> list:
+    """What rank 0 makes of gather_top_domains' result: per row the
+    union's first T = tops[r] domains in the contract's order as
+    ((hash, count) pairs, exact, bound). bound = S, the sum of the
+    serving shards' cut-offs: a domain that no shard reported holds at
+    most S matches, so the row is exact iff one shard serves, or S == 0,
+    or the T-th count is larger than S. The counts are exact either
+    way."""
+    pad = U32_MAX + 1
+    union, total = union.cpu().numpy(), total.cpu().numpy()
+    out = []
+    for r, T in enumerate(tops):
+        keep = (union[r] < pad) & (total[r] > 0)
+        hs, cs = union[r][keep], total[r][keep]
+        order = np.lexsort((hs, -cs))[:T]
+        pairs = tuple((int(hs[i]), int(cs[i])) for i in order)
+        S = int(cut[r])
+        c_T = pairs[T - 1][1] if len(pairs) >= T else 0
+        out.append((pairs, W == 1 or S == 0 or c_T > S, S))
+    return out
 
 
 def rrf_fuse(ids_lists: list[torch.Tensor], score_lists: list[torch.Tensor],
@@ -366,9 +425,28 @@ class DistributedQueryPlane:
             # all of them take this branch together)
             facet_sum = self.fabric.all_gather(
                 hits.facets.to(self.fabric.device)).sum(0).to(torch.int32)
+        top_reports = None
+        if hits.dom_top is not None:
+            # top domains: gather every shard's report (round 1); the
+            # union's exact counts take one more gather (round 2, in
+            # gather_top_domains). Only for a batch with a top row; every
+            # rank holds the same spec and takes the branch
+            top_reports = self.fabric.all_gather(
+                hits.dom_top.to(self.fabric.device).contiguous())
         tp = mark("plane.gather", tp)
+        top_merged = None
+        if top_reports is not None:
+            top_merged = gather_top_domains(
+                top_reports, hits.dom_tally.lookup, self.fabric.all_gather)
+            tp = mark("plane.topdomains", tp)
         if self.fabric.rank != 0:
             return None
+        top_domains = None
+        if top_merged is not None:
+            # rank 0 packed the spec before the first collective
+            top_domains = rank_top_domains(
+                *top_merged, W=top_reports.shape[0],
+                tops=[t for t in facets.top if t > 0])
         W, _, k = bm_s.shape
         bm_s = bm_s.permute(1, 0, 2).reshape(B, W * k)
         bm_i = bm_i.permute(1, 0, 2).reshape(B, W * k)
@@ -399,7 +477,8 @@ class DistributedQueryPlane:
         return FusedHits(ids=ids, scores=scores, bm25_ids=bm_i,
                          bm25_scores=bm_s, dense_ids=dn_i,
                          dense_scores=dn_s,
-                         degraded=self.fabric.degraded, facets=facet_sum)
+                         degraded=self.fabric.degraded, facets=facet_sum,
+                         top_domains=top_domains)
 
     def _search_overlapped(self, queries_terms, query_emb, encode_fn,
                            B, dim, use_dense, phase_t=None,
@@ -439,7 +518,7 @@ class DistributedQueryPlane:
             for t in mask or ():
                 t.record_stream(self._bm25_stream)
         self._bm25_stream.wait_stream(main)
-        counts = None
+        counts = dom_top = tally = None
         with torch.cuda.stream(self._bm25_stream):
             if facets is None:
                 bm_vals, bm_idx = self.shard.search_bm25(
@@ -448,10 +527,11 @@ class DistributedQueryPlane:
             else:
                 # the counts ride the side stream with the scores they
                 # read; main waits for that stream before the gathers
-                bm_vals, bm_idx, counts = self.shard.search_bm25_facets(
-                    terms, self.k, facets,
-                    scores_buf=self._get_scores_buf(B), filters=filters,
-                    _mask=mask)
+                bm_vals, bm_idx, counts, dom_top, tally = \
+                    self.shard.search_bm25_top(
+                        terms, self.k, facets,
+                        scores_buf=self._get_scores_buf(B), filters=filters,
+                        _mask=mask)
             bm_ids = self.shard.to_global(bm_idx)
         tp = mark("ov.bm25", tp)
         if encode_shard is not None:
@@ -478,7 +558,7 @@ class DistributedQueryPlane:
         main.wait_stream(self._bm25_stream)
         return ShardHits(bm25_scores=bm_vals, bm25_ids=bm_ids,
                          dense_scores=dn_vals, dense_ids=dn_ids,
-                         facets=counts)
+                         facets=counts, dom_top=dom_top, dom_tally=tally)
 
     def _broadcast_terms(self, queries_terms, B, filters=None):
         """-> (terms, filters) of a batch without term operands."""
@@ -563,15 +643,22 @@ class DistributedQueryPlane:
         if packed is not None:
             hashes = [h for lst in packed.lists for h in lst]
             head = torch.tensor([len(packed.edges), len(packed.langs),
-                                 len(packed.rows), len(hashes)],
+                                 len(packed.rows),
+                                 len(hashes) | (_HAS_TOP if packed.top
+                                                else 0)],
                                 dtype=torch.int64)
             flat = [*packed.edges, *packed.langs, *packed.rows,
-                    *(len(lst) for lst in packed.lists), *hashes]
+                    *(len(lst) for lst in packed.lists), *hashes,
+                    *packed.top]
         head = head.to(dev)
         self.fabric.broadcast(head)
         E, L, R, H = head.cpu().tolist()
+        # a spec without top domains is broadcast as it always was
+        has_top, H = bool(H & _HAS_TOP), H & ~_HAS_TOP
+        n_top = R if has_top else 0
         body = (torch.tensor(flat, dtype=torch.int64) if packed is not None
-                else torch.zeros(E + L + 2 * R + H, dtype=torch.int64))
+                else torch.zeros(E + L + 2 * R + H + n_top,
+                                 dtype=torch.int64))
         body = body.to(dev)
         self.fabric.broadcast(body)
         v = body.cpu().tolist()
@@ -584,7 +671,8 @@ class DistributedQueryPlane:
             lists.append(tuple(v[at:at + n]))
             at += n
         return PackedFacets(edges=tuple(edges), langs=tuple(langs),
-                            rows=tuple(rows), lists=tuple(lists))
+                            rows=tuple(rows), lists=tuple(lists),
+                            top=tuple(v[at:at + n_top]))
 
     def _broadcast_lists(self, filters: list, lists: dict, B: int) -> None:
         """The domain lists of a batch whose flag bits announce some:

@@ -14,7 +14,7 @@ DEFAULT_BASE = "http://127.0.0.1:8080"
 
 def _search_params(query, limit, mode, include_domains, exclude_domains,
                    recency_days, facets=False,
-                   facet_domains=None) -> dict[str, Any]:
+                   facet_domains=None, top_domains=0) -> dict[str, Any]:
     """/search parameters; the domain lists go comma-separated, and only
     when given."""
     params: dict[str, Any] = {"q": query, "limit": limit, "mode": mode}
@@ -28,6 +28,8 @@ def _search_params(query, limit, mode, include_domains, exclude_domains,
         params["facets"] = 1
         if facet_domains:
             params["facet_domains"] = ",".join(facet_domains)
+        if top_domains:
+            params["top_domains"] = int(top_domains)
     return params
 
 
@@ -52,15 +54,16 @@ class InfoMeshClient:
     def search(self, query: str, limit: int = 10, mode: str = "auto",
                include_domains=None, exclude_domains=None,
                recency_days: float = 0, facets: bool = False,
-               facet_domains=None):
+               facet_domains=None, top_domains: int = 0):
         """include_domains / exclude_domains: exact domains to allow /
         block; recency_days: only documents crawled that recently.
         facets: return {"results", "total_matches", "facets"} instead of
         the hit list, with counts over every matching document;
-        facet_domains: the domains to count."""
+        facet_domains: the domains to count; top_domains: how many of
+        the match set's top domains to add to the facets (at most 32)."""
         r = self._client.get("/search", params=_search_params(
             query, limit, mode, include_domains, exclude_domains,
-            recency_days, facets, facet_domains))
+            recency_days, facets, facet_domains, top_domains))
         r.raise_for_status()
         return _search_result(r.json(), facets)
 
@@ -114,11 +117,11 @@ class AsyncInfoMeshClient:
     async def search(self, query: str, limit: int = 10, mode: str = "auto",
                      include_domains=None, exclude_domains=None,
                      recency_days: float = 0, facets: bool = False,
-                     facet_domains=None):
+                     facet_domains=None, top_domains: int = 0):
         """As InfoMeshClient.search."""
         r = await self._client.get("/search", params=_search_params(
             query, limit, mode, include_domains, exclude_domains,
-            recency_days, facets, facet_domains))
+            recency_days, facets, facet_domains, top_domains))
         r.raise_for_status()
         return _search_result(r.json(), facets)
 

@@ -258,33 +258,56 @@ def with_filter_tokens(query: str, include=(), exclude=(),
 
 # A facet request travels to the engine as one token at the end of the
 # query text, like the filters do: facets:@ and the domains to count,
-# comma-separated (facets:@ alone: no domain counts). No other code
-# reads or writes this syntax.
-_FACET_RE = re.compile(r"(?<!\S)facets:@(\S*)(?!\S)")
+# comma-separated (facets:@ alone: no domain counts). A request for the
+# match set's top T domains writes T between the colon and the @:
+# facets:20@a.com,b.com. No other code reads or writes this syntax.
+_FACET_RE = re.compile(r"(?<!\S)facets:(\d*)@(\S*)(?!\S)")
+
+
+def _facet_names(domains) -> tuple[str, ...]:
+    """Names as with_filter_tokens writes a list's."""
+    return _site_names(",".join(
+        re.sub(r"[\s,]+", "_", d.strip()) for d in domains or ()
+        if d and d.strip()))
 
 
 def with_facet_token(query: str, domains=()) -> str:
     """`query` with the token appended that parse_facet_token reads
-    back: the one writer of that syntax. Names are written as
-    with_filter_tokens writes a list's."""
-    names = _site_names(",".join(
-        re.sub(r"[\s,]+", "_", d.strip()) for d in domains or ()
-        if d and d.strip()))
-    return f"{query} facets:@{','.join(names)}".lstrip()
+    back: the one writer of that syntax for a request without top
+    domains (with_facet_request writes the others)."""
+    return f"{query} facets:@{','.join(_facet_names(domains))}".lstrip()
+
+
+def with_facet_request(query: str, domains=(), top: int = 0) -> str:
+    """with_facet_token for a request that may ask for its top `top`
+    domains as well; top = 0 writes with_facet_token's token."""
+    if not top:
+        return with_facet_token(query, domains)
+    return f"{query} facets:{int(top)}@" \
+           f"{','.join(_facet_names(domains))}".lstrip()
+
+
+def parse_facet_request(query: str
+                        ) -> tuple[str, tuple[str, ...] | None, int]:
+    """(text without the token, domains to count, top domains asked for)
+    of a query with_facet_token or with_facet_request wrote;
+    (query, None, 0) when it carries no token. The number is whatever
+    was written: the reader clamps it."""
+    found: list[tuple[tuple[str, ...], int]] = []
+
+    def _sub(m: re.Match) -> str:
+        found.append((_site_names(m.group(2)), int(m.group(1) or 0)))
+        return ""
+    text = _FACET_RE.sub(_sub, query)
+    if not found:
+        return query, None, 0
+    return re.sub(r"\s{2,}", " ", text).strip(), *found[-1]
 
 
 def parse_facet_token(query: str) -> tuple[str, tuple[str, ...] | None]:
     """(text without the token, domains to count) of a query
     with_facet_token wrote; (query, None) when it carries no token."""
-    found: list[tuple[str, ...]] = []
-
-    def _sub(m: re.Match) -> str:
-        found.append(_site_names(m.group(1)))
-        return ""
-    text = _FACET_RE.sub(_sub, query)
-    if not found:
-        return query, None
-    return re.sub(r"\s{2,}", " ", text).strip(), found[-1]
+    return parse_facet_request(query)[:2]
 
 
 # ---------------------------------------------------- related searches

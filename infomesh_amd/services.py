@@ -11,6 +11,7 @@ from __future__ import annotations
 import logging
 import math
 import time
+from collections import Counter
 from dataclasses import dataclass, field
 from typing import Any
 
@@ -25,17 +26,18 @@ from .crawler.worker import CrawlResult, CrawlWorker
 from .engine import HybridEngine
 from .errors import GpuExtensionMissing, InfoMeshError
 from .crawler.lang_detect import known_languages
-from .index.doc_attrs import (FACET_MAX_DOMS, DocFilter, FacetCounts,
-                              FacetSpec, pack_pred_sets)
+from .index.doc_attrs import (FACET_MAX_DOMS, TOP_DOMAINS_MAX, DocFilter,
+                              FacetCounts, FacetSpec, pack_pred_sets)
 from .index.gpu_index import bm25_term_ids
 from .index.link_graph import LinkGraph
 from .index.local_store import Document, LocalStore
 from .search.batcher import QueryBatcher
 from .search.cache import QueryCache
 from .search.facets import compute_facets
-from .search.nlp import (RelatedSearchTracker, parse_facet_token,
-                         parse_query_filters, parse_term_operators,
-                         with_facet_token, with_filter_tokens)
+from .search.nlp import (RelatedSearchTracker, parse_facet_request,
+                         parse_facet_token, parse_query_filters,
+                         parse_term_operators, with_facet_request,
+                         with_filter_tokens)
 from .search.passage import fast_snippet
 from .search.query import (SearchResponse, preprocess_query,
                            search_hybrid, search_local)
@@ -102,6 +104,9 @@ class AppContext:
     # governor.py:49-74 semantics)
     governor: Any = None
     otlp: Any = None   # utils.observability.OtlpExporter (off by default)
+    # the engine's hash -> domain name map was refilled from the store
+    # (_domain_label does it once, on the first unknown hash)
+    _domain_names_loaded: bool = False
 
     # ------------------------------------------------------------ build
     @classmethod
@@ -296,7 +301,7 @@ class AppContext:
                deduct: bool = True, include_domains=None,
                exclude_domains=None,
                recency_days: float = 0, facets: bool = False,
-               facet_domains=()) -> SearchResponse:
+               facet_domains=(), top_domains: int = 0) -> SearchResponse:
         """Unified search entry (reference mcp/handlers.py:382 flow):
         cache -> credits -> local/hybrid/distributed -> cache.
 
@@ -318,7 +323,17 @@ class AppContext:
         more is a ValueError; they count by 32-bit hash). Served from
         FTS, the counts cover the returned hits ("scope": "results")
         and total_matches is None. A request without facets gets the
-        response it always got."""
+        response it always got.
+
+        top_domains (with facets): T > 0 adds "top_domains" to the
+        facets, {name: count} of the first T domains of the whole match
+        set by count, then by 32-bit hash; at most
+        doc_attrs.TOP_DOMAINS_MAX, more is a ValueError. The counts are
+        exact over all shards. "top_domains_exact" says whether the T
+        names are surely the true first T; when it is False a domain
+        that is not shown may hold up to "top_domains_bound" matches.
+        A hash whose name is unknown reads "#%08x". Served from FTS it
+        is the hits' most common T domains, without those two keys."""
         from .utils.plugins import GLOBAL_PLUGINS
         query = GLOBAL_PLUGINS.run("pre_search", query, mode=mode)
         # facets:@... is the serving path's own syntax (_engine_search
@@ -336,6 +351,10 @@ class AppContext:
                                        exclude_domains, after)
         limit = limit or self.config.search.max_results
         fdoms = None
+        top = int(top_domains or 0) if facets else 0
+        if top < 0 or top > TOP_DOMAINS_MAX:
+            raise ValueError(
+                f"top_domains = {top}; the cap is {TOP_DOMAINS_MAX}")
         if facets:
             fdoms = tuple(dict.fromkeys(
                 d.strip().lower() for d in facet_domains or ()
@@ -344,10 +363,12 @@ class AppContext:
                 raise ValueError(
                     f"{len(fdoms)} facet domains; the cap is "
                     f"{FACET_MAX_DOMS} per query")
-        # None leaves a plain request's key as it always was
+        # None leaves a plain request's key as it always was, and one
+        # without top domains the key a facet request always had
         key = QueryCache.make_key(query, limit=limit, mode=mode,
                                   facets=None if fdoms is None
-                                  else list(fdoms))
+                                  else list(fdoms),
+                                  top_domains=top or None)
         if use_cache:
             cached = self.cache.get(key)
             if cached is not None:
@@ -386,7 +407,8 @@ class AppContext:
                 # dense exactly once; results are hydrated from the
                 # LocalStore (round-1 double-fusion fix)
                 resp = self._engine_search(query, limit, mode,
-                                           facet_domains=fdoms)
+                                           facet_domains=fdoms,
+                                           top_domains=top)
             else:
                 resp = search_hybrid(
                     self.store, None, query, limit=limit,
@@ -406,6 +428,10 @@ class AppContext:
             resp.facets = {"scope": "results", "domains": over["domains"],
                            "languages": over["languages"],
                            "date_ranges": over["dates"]}
+            if top:
+                resp.facets["top_domains"] = dict(
+                    Counter(r.domain for r in resp.results
+                            if r.domain).most_common(top))
         resp = GLOBAL_PLUGINS.run("post_search", resp, query=query)
         if use_cache:
             self.cache.put(key, resp)
@@ -464,8 +490,12 @@ class AppContext:
         # refuses one on the caller's thread; only a direct submit can
         # bring one) is cut to its first FACET_MAX_DOMS names, never
         # raised.
-        asked = [(text, doms if doms is None else doms[:FACET_MAX_DOMS])
-                 for text, doms in map(parse_facet_token, queries)]
+        # A top-domain count over the cap is clamped likewise.
+        asked, tops = [], []
+        for text, doms, top in map(parse_facet_request, queries):
+            asked.append((text,
+                          doms if doms is None else doms[:FACET_MAX_DOMS]))
+            tops.append(min(top, TOP_DOMAINS_MAX) if doms is not None else 0)
         queries = [text for text, _ in asked]
         spec = None
         if any(doms is not None for _, doms in asked):
@@ -474,7 +504,8 @@ class AppContext:
                 date_edges=tuple(now - d * 86400 for d in _DATE_AGES_D)
                 + (now + 1,),
                 languages=known_languages(),
-                domains=tuple(doms for _, doms in asked))
+                domains=tuple(doms for _, doms in asked),
+                top_domains=tuple(tops) if any(tops) else ())
         filters = None
         parsed: list = [None] * len(queries)
         if self.config.gpu.filters:
@@ -565,11 +596,26 @@ class AppContext:
         return {"scope": "matches", "domains": dict(c.domains),
                 "languages": langs, "date_ranges": ranges}
 
+    def _domain_label(self, h: int) -> str:
+        """The name of a top domain's hash: the engine's map; on a miss
+        (an engine started from a manifest never saw the names) the map
+        is refilled once from the store's domains; "#%08x" for a hash
+        that is still unknown."""
+        name = self.engine.domain_name(h)
+        if name is None and not self._domain_names_loaded:
+            self._domain_names_loaded = True
+            for d in self.store.all_domains():
+                self.engine.note_domain(d)
+            name = self.engine.domain_name(h)
+        return name if name is not None else "#%08x" % h
+
     def _engine_search(self, query: str, limit: int, mode: str,
-                       facet_domains=None) -> SearchResponse:
+                       facet_domains=None,
+                       top_domains: int = 0) -> SearchResponse:
         """GPU-plane search via the micro-batcher (fused once on the
         plane, hydrated batch-wide in _batch_execute). facet_domains:
-        None, or the domains to count of a request with facets."""
+        None, or the domains to count of a request with facets;
+        top_domains: how many top domains such a request asks for."""
         t0 = time.time()
         trace = None
         if self.otlp is not None and self.otlp.enabled:
@@ -593,7 +639,7 @@ class AppContext:
         # a typed one first; one that still came this way goes here.
         eff = parse_facet_token(eff)[0]
         sent = eff if facet_domains is None \
-            else with_facet_token(eff, facet_domains)
+            else with_facet_request(eff, facet_domains, top_domains)
         batcher = self.ensure_batcher()
         if trace is not None:
             with trace.span("engine"):
@@ -617,6 +663,11 @@ class AppContext:
         if facet_domains is not None and counts is not None:
             resp.total_matches = counts.total
             resp.facets = self._facets_dict(counts)
+            if counts.top_domains is not None:
+                resp.facets["top_domains"] = {
+                    self._domain_label(h): n for h, n in counts.top_domains}
+                resp.facets["top_domains_exact"] = counts.top_domains_exact
+                resp.facets["top_domains_bound"] = counts.top_domains_bound
         return resp
 
     def fetch_page(self, url: str) -> Document | None:
