@@ -76,13 +76,16 @@ def create_app(ctx: AppContext, api_key: str = "",
     def search(q: str, limit: int = 10, mode: str = "auto",
                include_domains: str = "", exclude_domains: str = "",
                recency_days: float = 0, facets: int = 0,
-               facet_domains: str = "", top_domains: int = 0):
+               facet_domains: str = "", top_domains: int = 0,
+               per_domain: int = 0):
         """include_domains / exclude_domains: comma-separated exact
         domains to allow / block; recency_days: crawled that recently.
         facets=1 adds "total_matches" and "facets" to the answer
         (AppContext.search says what they cover); facet_domains:
         comma-separated domains to count; top_domains: with facets=1,
-        how many of the match set's top domains to add (at most 32)."""
+        how many of the match set's top domains to add (at most 32);
+        per_domain: at most that many hits per site, 1 .. 4, 0 for no
+        cap (AppContext.search says what the cap covers)."""
         if not q.strip():
             raise HTTPException(400, "empty query")
         kw = {}
@@ -91,13 +94,15 @@ def create_app(ctx: AppContext, api_key: str = "",
                   "facet_domains": [d for d in facet_domains.split(",") if d]}
             if top_domains:
                 kw["top_domains"] = top_domains
+        if per_domain:
+            kw["per_domain"] = per_domain
         try:
             resp = ctx.search(
                 q, limit=min(limit, 50), mode=mode,
                 include_domains=[d for d in include_domains.split(",") if d],
                 exclude_domains=[d for d in exclude_domains.split(",") if d],
                 recency_days=recency_days, **kw)
-        except ValueError as e:      # domain lists over the cap
+        except ValueError as e:      # a list or per_domain over its cap
             raise HTTPException(400, str(e)) from e
         out = {"query": q, "mode": resp.mode,
                "elapsed_ms": round(resp.elapsed_ms, 2),

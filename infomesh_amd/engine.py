@@ -20,7 +20,8 @@ import torch
 from .index.doc_attrs import (DocFilter, FacetCounts, FacetSpec, TermOps,
                               domain_hash, facet_results, pack_attrs,
                               pack_facets)
-from .index.gpu_index import CpuShard, GpuShard, bm25_term_ids
+from .index.gpu_index import (CpuShard, GpuShard, bm25_term_ids,
+                              per_domain_caps)
 from .index.local_store import (Document, LocalStore, SearchHit,
                                 extract_domain)
 from .parallel.fabric import Fabric
@@ -243,7 +244,8 @@ class HybridEngine:
                     use_dense: bool | None = None,
                     filters: list[DocFilter | None] | None = None,
                     require: list[tuple[str, ...] | None] | None = None,
-                    exclude: list[tuple[str, ...] | None] | None = None
+                    exclude: list[tuple[str, ...] | None] | None = None,
+                    per_domain: list[int | None] | None = None
                     ) -> list[list[SearchHit]]:
         """Batched search: ONE collective plane.search_batch for the
         whole list (the batcher's execute path). Fusion happens exactly
@@ -252,16 +254,22 @@ class HybridEngine:
         DocFilter or None per query, applied inside the shards' top-k
         selection. require / exclude: one tuple of words (or None) per
         query; a hit holds every required word and no excluded one, on
-        both planes (term_ops_for says how words become operands)."""
+        both planes (term_ops_for says how words become operands).
+        per_domain: one int or None per query; a query with m, 1 <= m
+        <= 4, gets at most m hits per domain, chosen over each plane's
+        whole score row and again over the fused list
+        (DistributedQueryPlane.search_batch says it in full); 0 or None:
+        no cap. Outside 0 .. 4 is a ValueError."""
         return self._search_many(queries, limit, use_dense, filters,
-                                 require, exclude, None)[0]
+                                 require, exclude, None, per_domain)[0]
 
     def search_with_facets(self, queries: list[str], limit: int = 10,
                            use_dense: bool | None = None,
                            filters: list[DocFilter | None] | None = None,
                            require: list[tuple[str, ...] | None] | None = None,
                            exclude: list[tuple[str, ...] | None] | None = None,
-                           facets: FacetSpec | None = None
+                           facets: FacetSpec | None = None,
+                           per_domain: list[int | None] | None = None
                            ) -> tuple[list[list[SearchHit]],
                                       list[FacetCounts | None]]:
         """search_many plus, per query, the counts of a FacetSpec over
@@ -272,12 +280,14 @@ class HybridEngine:
         full). The hits are those of search_many; a query whose entry in
         facets.domains is None (or missing) gets None. A row of
         facets.top_domains adds the first T domains of the match set by
-        count (FacetCounts.top_domains, as hashes: domain_name)."""
+        count (FacetCounts.top_domains, as hashes: domain_name).
+        per_domain: as in search_many; it caps the hits, never the
+        counts."""
         return self._search_many(queries, limit, use_dense, filters,
-                                 require, exclude, facets)
+                                 require, exclude, facets, per_domain)
 
     def _search_many(self, queries, limit, use_dense, filters, require,
-                     exclude, facets):
+                     exclude, facets, per_domain=None):
         """The one body of search_many and search_with_facets ->
         (hits per query, FacetCounts or None per query)."""
         if self.shard.n_docs == 0 or not queries:
@@ -285,6 +295,7 @@ class HybridEngine:
         B = len(queries)
         if facets is not None and len(facets.domains) > B:
             raise ValueError("facets: more domain lists than queries")
+        per_domain = per_domain_caps(per_domain, B)
         term_ops = None
         if require is not None or exclude is not None:
             require = require or [None] * B
@@ -316,12 +327,15 @@ class HybridEngine:
                        if any(f is not None for f in filters) else None)
         if term_ops is not None:
             term_ops = term_ops + [None] * (Bp - B)
+        if per_domain is not None:
+            per_domain = per_domain + [0] * (Bp - B)
         # padding rows are past the end of facets.domains: never counted
         packed = pack_facets(facets, Bp)
         fused = self.plane.search_batch(
             terms, emb, B=Bp, dim=emb.shape[1] if emb is not None else 384,
             n_results=limit, use_dense=use_dense and emb is not None,
-            filters=filters, term_ops=term_ops, facets=packed)
+            filters=filters, term_ops=term_ops, facets=packed,
+            per_domain=per_domain)
         if fused is None:
             return [[] for _ in queries], [None] * B
         counts: list[FacetCounts | None] = [None] * B

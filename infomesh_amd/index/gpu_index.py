@@ -46,6 +46,26 @@ BM25_VOCAB = 1 << 17
 # optimize() (GPU-side merge) — the FTS5 automerge analogue
 MAX_SEGMENTS = 16
 
+# per-domain cap (ops/csrc/collapse.hip): the largest m a row may ask
+# for, and the most the [m, R, D] u64 workspace of one plane may take;
+# more capped rows than fit are processed in slices
+COLLAPSE_M_MAX = 4
+COLLAPSE_WS_BYTES = 256 << 20
+
+
+def per_domain_caps(per_domain, B: int) -> list[int] | None:
+    """One cap per row from a per_domain argument (one int or None per
+    row, or None): None when no row is capped. A cap outside
+    0 .. COLLAPSE_M_MAX is a ValueError."""
+    if per_domain is None:
+        return None
+    caps = [int(m or 0) for m in per_domain]
+    assert len(caps) == B, "per_domain: one entry per query"
+    if any(not 0 <= m <= COLLAPSE_M_MAX for m in caps):
+        raise ValueError(
+            f"per_domain: {caps}; 0 (no cap) or 1 <= m <= {COLLAPSE_M_MAX}")
+    return caps if any(caps) else None
+
 # \w+ covers all unicode letters/digits (FTS5 unicode61 analogue);
 # diacritics are NFKD-folded below like unicode61 remove_diacritics
 _WORD_RE = re.compile(r"\w+")
@@ -121,6 +141,11 @@ class ShardHits:
     # when no row asked
     dom_top: torch.Tensor | None = None
     dom_tally: DomainTally | None = None
+    # [B, k] i32: the hits' domain words (w2 of the attribute record, 0
+    # at padding), for the query plane's cap on the merged lists; None
+    # when no row of the batch carries a per-domain cap
+    bm25_dom: torch.Tensor | None = None
+    dense_dom: torch.Tensor | None = None
 
 
 @dataclass
@@ -169,6 +194,9 @@ class GpuShard:
         # workspace of ops/csrc/domtop.hip
         self._dom_tables = None
         self._dom_ws: torch.Tensor | None = None
+        # [m, R, D] u64 workspaces of ops/csrc/collapse.hip, one per
+        # plane (the planes may run on two streams)
+        self._collapse_ws: dict[str, torch.Tensor] = {}
         self._topk = None
         self._topk_dense = None
         self._topk_pruned = None    # dense selector over block maxima
@@ -741,7 +769,8 @@ class GpuShard:
     def hbm_bytes(self) -> int:
         total = sum(s.hbm_bytes() for s in self.segments)
         for t in (self._emb_buf, self._gid_buf, self._attr_buf,
-                  self._dom_ws, *(self._dom_tables or ())):
+                  self._dom_ws, *self._collapse_ws.values(),
+                  *(self._dom_tables or ())):
             if t is not None:
                 total += t.numel() * t.element_size()
         return total
@@ -764,6 +793,49 @@ class GpuShard:
             self._dom_ws = torch.empty(R * D, device=self.device,
                                        dtype=torch.int32)
         return self._dom_ws[:R * D].view(R, D)
+
+    def _collapse_rows(self, plane: str, scores: torch.Tensor, k: int,
+                       caps: list[int], mask, vals: torch.Tensor,
+                       idx: torch.Tensor) -> None:
+        """Overwrite the capped rows of a plane's top-k (vals, idx
+        [B, k]) with the first k of their capped sets, exact over the
+        whole score row (ops/csrc/collapse.hip): domain_best x m and
+        collapse_select over the scores and the mask the top-k read.
+        plane: "bm25" (eligible: passes the mask and score > 0) or
+        "dense" (passes the mask). Rows are grouped by m and taken in
+        slices whose workspace stays within COLLAPSE_WS_BYTES."""
+        from ..ops import kernels as K
+        dom_keys, dom_id = self._domain_tables()
+        D = dom_keys.numel()
+        for m in sorted(set(caps) - {0}):
+            rows = [b for b, c in enumerate(caps) if c == m]
+            step = max(1, COLLAPSE_WS_BYTES // (m * D * 8))
+            for lo in range(0, len(rows), step):
+                part = rows[lo:lo + step]
+                need = m * len(part) * D
+                ws = self._collapse_ws.get(plane)
+                if ws is None or ws.numel() < need:
+                    ws = self._collapse_ws[plane] = torch.empty(
+                        need, device=self.device, dtype=torch.int64)
+                # one upload: the kernel's rows and the rows to overwrite
+                rows_t = torch.tensor(part, dtype=torch.int32)
+                rows_d = rows_t.to(self.device, non_blocking=True)
+                best = K.domain_best(
+                    scores, rows_t, dom_id, D, m, plane == "bm25",
+                    mask=None if mask is None else mask[0],
+                    row_pred=None if mask is None else mask[1],
+                    out=ws[:need].view(m, len(part), D),
+                    rows_device=rows_d)
+                c_vals, c_idx = K.collapse_select(best, k)
+                at = rows_d.long()
+                vals.index_copy_(0, at, c_vals)
+                idx.index_copy_(0, at, c_idx.to(idx.dtype))
+
+    def hit_domains(self, idx: torch.Tensor) -> torch.Tensor:
+        """[B, k] shard-local columns (-1 pad) -> [B, k] i32 domain words
+        (w2 of the attribute record), 0 at padding."""
+        w2 = self.attrs[:, 2][idx.clamp(min=0).long()]
+        return torch.where(idx >= 0, w2, torch.zeros_like(w2))
 
     # ----------------------------------------------------------- search
     def _get_topk(self):
@@ -862,7 +934,8 @@ class GpuShard:
 
     def search_bm25(self, queries_terms: list[np.ndarray], k: int,
                     scores_buf: torch.Tensor | None = None,
-                    mark=None, filters=None, _mask=None, term_ops=None
+                    mark=None, filters=None, _mask=None, term_ops=None,
+                    per_domain=None
                     ) -> tuple[torch.Tensor, torch.Tensor]:
         """BM25 plane only (needs terms, not embeddings) — callable on a
         side stream to overlap with query encoding. One kernel launch
@@ -875,24 +948,33 @@ class GpuShard:
         produced and the masked top-k streams the matrix once more.
         term_ops: one TermOps or None per query; a row with operands
         selects among the documents that hold every required and no
-        excluded term, and masks the batch like a filter does."""
+        excluded term, and masks the batch like a filter does.
+        per_domain: one int or None per query; a row with a cap m
+        (1 .. COLLAPSE_M_MAX) returns at most m documents per domain,
+        the first k of its capped set over the whole score row, in
+        score order with ties by ascending column, bit for bit
+        (ops/csrc/collapse.hip). Domains compare by their 32-bit hash,
+        as filters and facets compare them: a hash collision can only
+        over-collapse. The other rows are what they are without it."""
         return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
-                                _mask, term_ops, None)[:2]
+                                _mask, term_ops, None, per_domain)[:2]
 
     def search_bm25_top(self, queries_terms: list[np.ndarray], k: int,
                         facets, scores_buf: torch.Tensor | None = None,
-                        mark=None, filters=None, _mask=None, term_ops=None):
+                        mark=None, filters=None, _mask=None, term_ops=None,
+                        per_domain=None):
         """search_bm25_facets plus the top domains of the rows that ask
         for them: -> (values, indices, counts, dom_top, dom_tally), the
         last two as ShardHits holds them (None when no row asks)."""
         return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
                                 _mask, term_ops,
-                                pack_facets(facets, len(queries_terms)))
+                                pack_facets(facets, len(queries_terms)),
+                                per_domain)
 
     def search_bm25_facets(self, queries_terms: list[np.ndarray], k: int,
                            facets, scores_buf: torch.Tensor | None = None,
                            mark=None, filters=None, _mask=None,
-                           term_ops=None
+                           term_ops=None, per_domain=None
                            ) -> tuple[torch.Tensor, torch.Tensor,
                                       torch.Tensor | None]:
         """search_bm25 that also counts facets over every matching
@@ -905,16 +987,18 @@ class GpuShard:
         pass-1 histogram."""
         return self._bm25_plane(queries_terms, k, scores_buf, mark, filters,
                                 _mask, term_ops,
-                                pack_facets(facets, len(queries_terms)))[:3]
+                                pack_facets(facets, len(queries_terms)),
+                                per_domain)[:3]
 
     def _bm25_plane(self, queries_terms, k, scores_buf, mark, filters,
-                    _mask, term_ops, facets):
+                    _mask, term_ops, facets, per_domain=None):
         import time as _time
         from ..ops import kernels as K
         if mark is None:
             def mark(name, t0):
                 return t0
         B = len(queries_terms)
+        caps = per_domain_caps(per_domain, B)
         dev = self.device
         N = self.n_docs
         k = min(k, N)
@@ -999,7 +1083,11 @@ class GpuShard:
             out = topk(scores, k, ext_hist1=hist)
         else:
             out = topk(scores, k, mask=mask[0], row_pred=mask[1])
-        mark("shard.bm25topk", tp)
+        tp = mark("shard.bm25topk", tp)
+        if caps is not None:
+            self._collapse_rows("bm25", scores, k, caps, mask, out[0],
+                                out[1])
+            mark("shard.bm25collapse", tp)
         self._bm25_scores_buf = scores
         return out[0], out[1], counts, dom_top, tally
 
@@ -1009,7 +1097,8 @@ class GpuShard:
                phase_t: dict | None = None,
                filters: list[DocFilter | None] | None = None,
                term_ops: list[TermOps | None] | None = None,
-               facets: FacetSpec | None = None) -> ShardHits:
+               facets: FacetSpec | None = None,
+               per_domain: list[int | None] | None = None) -> ShardHits:
         """Score all queries against this shard; returns fixed-size
         top-k with global ids (the per-peer result cap analogue,
         reference p2p/routing.py:48). filters: one DocFilter or None per
@@ -1021,7 +1110,11 @@ class GpuShard:
         leaves the row all padding). facets: a FacetSpec (or
         PackedFacets); ShardHits.facets then holds the counts over every
         matching document of the rows it names, and the hits are what
-        they are without it."""
+        they are without it. per_domain: one int or None per query, as
+        in search_bm25; both planes of a capped row return at most m
+        documents per domain (the dense plane over every document that
+        passes the mask), and ShardHits.bm25_dom / dense_dom hold the
+        hits' domain words."""
         import time as _time
 
         def mark(name, t0):
@@ -1043,17 +1136,19 @@ class GpuShard:
         if facets is None:
             bm_vals, bm_idx = self.search_bm25(queries_terms, k,
                                                scores_buf=scores_buf,
-                                               mark=mark, _mask=mask)
+                                               mark=mark, _mask=mask,
+                                               per_domain=per_domain)
         else:
             bm_vals, bm_idx, counts, dom_top, tally = self.search_bm25_top(
                 queries_terms, k, facets, scores_buf=scores_buf, mark=mark,
-                _mask=mask)
+                _mask=mask, per_domain=per_domain)
         tp = _time.perf_counter()
 
         # --- dense plane ---
         if query_emb is not None and self.embeddings is not None:
             dn_vals, dn_idx = self.search_dense(query_emb, k, mark=mark,
-                                                _mask=mask)
+                                                _mask=mask,
+                                                per_domain=per_domain)
         else:
             dn_vals = torch.full((B, k), -float("inf"), device=dev)
             dn_idx = torch.full((B, k), -1, device=dev, dtype=torch.int32)
@@ -1062,13 +1157,28 @@ class GpuShard:
                          bm25_ids=self.to_global(bm_idx),
                          dense_scores=dn_vals,
                          dense_ids=self.to_global(dn_idx), facets=counts,
-                         dom_top=dom_top, dom_tally=tally)
+                         dom_top=dom_top, dom_tally=tally,
+                         **self._hit_dom_fields(per_domain, B, bm_idx,
+                                                dn_idx))
+
+    def _hit_dom_fields(self, per_domain, B: int, bm_idx, dn_idx) -> dict:
+        """ShardHits' bm25_dom / dense_dom of a batch with a capped row;
+        nothing otherwise."""
+        if per_domain_caps(per_domain, B) is None:
+            return {}
+        return {"bm25_dom": self.hit_domains(bm_idx),
+                "dense_dom": self.hit_domains(dn_idx)}
 
     def search_dense(self, query_emb: torch.Tensor, k: int,
-                     mark=None, filters=None, _mask=None, term_ops=None
+                     mark=None, filters=None, _mask=None, term_ops=None,
+                     per_domain=None
                      ) -> tuple[torch.Tensor, torch.Tensor]:
         """Dense (cosine) plane; runs after the query embedding exists.
-        filters, term_ops: as in search_bm25."""
+        filters, term_ops, per_domain: as in search_bm25, with every
+        document that passes the mask eligible, whatever its score. The
+        collapse kernels read the plane's score buffer after the top-k,
+        outside the captured graph: the buffer still holds the batch's
+        scores when a graph has replayed."""
         import time as _time
         from ..ops import kernels as K
         if mark is None:
@@ -1079,6 +1189,7 @@ class GpuShard:
         k = min(k, N)
         mask = _mask if _mask is not None else self._mask_for(filters, B,
                                                               term_ops)
+        caps = per_domain_caps(per_domain, B)
         tp = _time.perf_counter()
         emb = self.embeddings
         # hipGraph capture of the whole plane (GEMM + top-k passes, all
@@ -1105,7 +1216,12 @@ class GpuShard:
             # detach from the graph's static outputs (next replay
             # overwrites them)
             out = (vals.clone(), idx.clone())
-            mark("shard.dense+topk", tp)
+            tp = mark("shard.dense+topk", tp)
+            if caps is not None:
+                self._collapse_rows(
+                    "dense", self._get_dense_buf(B).reshape(B, N), k, caps,
+                    None, *out)
+                mark("shard.densecollapse", tp)
             return out
         d_scores = self._dense_gemm(query_emb, emb, B, N,
                                     with_bmax=mask is None)
@@ -1118,7 +1234,12 @@ class GpuShard:
         else:
             out = self._get_topk_dense()(d_scores, k, mask=mask[0],
                                          row_pred=mask[1])
-        mark("shard.densetopk", tp)
+        tp = mark("shard.densetopk", tp)
+        if caps is not None:
+            self._collapse_rows(
+                "dense", self._get_dense_buf(B).reshape(B, N), k, caps, mask,
+                *out)
+            mark("shard.densecollapse", tp)
         return out
 
     @staticmethod
@@ -1247,7 +1368,7 @@ class CpuShard(GpuShard):
 
     def search(self, queries_terms, query_emb, k: int = 100,
                scores_buf=None, phase_t=None, filters=None,
-               term_ops=None, facets=None) -> ShardHits:
+               term_ops=None, facets=None, per_domain=None) -> ShardHits:
         B = len(queries_terms)
         N = self.n_docs
         assert N > 0, "shard is empty"
@@ -1273,6 +1394,8 @@ class CpuShard(GpuShard):
         st = torch.from_numpy(scores)
         fail = self._fail_rows(filters, B, term_ops)
         bm_vals, bm_idx = self._masked_topk(st, fail, k)
+        caps = per_domain_caps(per_domain, B)
+        self._collapse_rows_np(st, k, caps, fail, True, bm_vals, bm_idx)
         counts = dom_top = tally = None
         packed = pack_facets(facets, B)
         if packed is not None:
@@ -1296,6 +1419,8 @@ class CpuShard(GpuShard):
         if query_emb is not None and self.embeddings is not None:
             d_scores = query_emb.float().cpu() @ self.embeddings.float().T
             dn_vals, dn_idx = self._masked_topk(d_scores, fail, k)
+            self._collapse_rows_np(d_scores, k, caps, fail, False, dn_vals,
+                                   dn_idx)
         else:
             dn_vals = torch.full((B, k), -float("inf"))
             dn_idx = torch.full((B, k), -1, dtype=torch.int64)
@@ -1308,7 +1433,27 @@ class CpuShard(GpuShard):
         return ShardHits(bm25_scores=bm_vals, bm25_ids=to_global(bm_idx),
                          dense_scores=dn_vals.float(),
                          dense_ids=to_global(dn_idx), facets=counts,
-                         dom_top=dom_top, dom_tally=tally)
+                         dom_top=dom_top, dom_tally=tally,
+                         **self._hit_dom_fields(per_domain, B, bm_idx,
+                                                dn_idx))
+
+    def _collapse_rows_np(self, scores: torch.Tensor, k: int, caps, fail,
+                          positive: bool, vals, idx) -> None:
+        """GpuShard._collapse_rows through the oracle
+        (ops/reference.collapse_topk_rows), row by row."""
+        if caps is None:
+            return
+        from ..ops.reference import collapse_topk_rows
+        dom_id = self._domain_tables()[1]
+        fail_np = None if fail is None else fail.numpy()
+        for b, m in enumerate(caps):
+            if m:
+                v, i = collapse_topk_rows(
+                    scores[b:b + 1].float(),
+                    None if fail_np is None else fail_np[b:b + 1], dom_id,
+                    [0], m, k, positive)
+                vals[b] = v[0].to(vals.dtype)
+                idx[b] = i[0].to(idx.dtype)
 
     def _domain_tables(self) -> tuple[torch.Tensor, torch.Tensor]:
         """GpuShard's tables, built with numpy."""

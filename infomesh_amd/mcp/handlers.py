@@ -43,14 +43,16 @@ class Handlers:
                    fetch_full_content: bool = False,
                    validate: bool = False, facets: bool = False,
                    facet_domains: list[str] | None = None,
-                   top_domains: int = 0,
+                   top_domains: int = 0, per_domain: int = 0,
                    **_) -> dict[str, Any]:
         """facets: add "total_matches" and "facets" (counts over every
         matching document when the engine serves the query, see
         AppContext.search); facet_domains: exact domains to count;
         top_domains: how many of the match set's top domains to add. Both
         fields are null when the domain lists went over the cap and the
-        hits were filtered after an unfiltered search."""
+        hits were filtered after an unfiltered search. per_domain: at
+        most that many hits per site, 1 .. 4 (AppContext.search says
+        what the cap covers on each serving path)."""
         if not query or not query.strip():
             raise InfoMeshError("SRCH001", "empty query")
         # Reference-style argument forms (infomesh mcp/tools.py:53-136):
@@ -85,6 +87,8 @@ class Handlers:
             if facets else {}
         if facets and top_domains:
             fkw["top_domains"] = int(top_domains)
+        if per_domain:
+            fkw["per_domain"] = int(per_domain)
         include = exclude = None
         if domain_allowlist:
             # nothing stored under an allowed name: keep the names, which
@@ -101,7 +105,8 @@ class Handlers:
             # no facets here: the search runs WITHOUT the lists, so its
             # counts would cover documents the hits below are filtered
             # down from; the answer carries null for both fields
-            resp = self.ctx.search(query, limit=limit * 2, mode=mode)
+            resp = self.ctx.search(query, limit=limit * 2, mode=mode,
+                                   per_domain=int(per_domain or 0))
         else:
             resp = self.ctx.search(query, limit=limit, mode=mode,
                                    include_domains=include,

@@ -41,6 +41,10 @@ TOOLS: list[dict] = [
                                 "description": "with facets: how many of "
                                                "the match set's top "
                                                "domains to add (<= 32)"},
+                "per_domain": {"type": "integer", "minimum": 0,
+                               "maximum": 4,
+                               "description": "at most this many hits per "
+                                              "site (0: no cap)"},
                 "explain": {"type": "boolean"},
                 "chunk_size": {"type": "integer"},
                 "answer_mode": {

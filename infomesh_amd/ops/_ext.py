@@ -126,6 +126,15 @@ _SIGNATURES: dict[str, list] = {
     "infomesh_domtop_chunk_docs": [],
     "infomesh_domtop_lds_slots": [],
     "infomesh_domtop_k_max": [],
+    "infomesh_domain_best": [c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int, c_int, c_long,
+                             c_long, c_int, c_int, c_int, c_int, c_void_p],
+    "infomesh_collapse_select": [c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_int, c_void_p],
+    "infomesh_collapse_m_max": [],
+    "infomesh_collapse_k_max": [],
+    "infomesh_collapse_chunk_docs": [],
+    "infomesh_collapse_lds_slots": [],
 }
 
 # Everything not listed here returns void. topk_*_u32: lengths;
@@ -133,8 +142,14 @@ _SIGNATURES: dict[str, list] = {
 # gemm_tile: tile code; gemm_bmax_width: columns per block maximum;
 # term_block_docs: documents per workgroup of term_bitmask; facet_*: the
 # chunk size and the slot layout of facet_counts; domtop_*: the chunk
-# size, the LDS table size and the K cap of csrc/domtop.hip.
+# size, the LDS table size and the K cap of csrc/domtop.hip; collapse_*:
+# the caps on m and k, the chunk size and the LDS table size of
+# csrc/collapse.hip.
 _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
+             "infomesh_collapse_m_max": c_int,
+             "infomesh_collapse_k_max": c_int,
+             "infomesh_collapse_chunk_docs": c_int,
+             "infomesh_collapse_lds_slots": c_int,
              "infomesh_domtop_chunk_docs": c_int,
              "infomesh_domtop_lds_slots": c_int,
              "infomesh_domtop_k_max": c_int,

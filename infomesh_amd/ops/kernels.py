@@ -774,6 +774,117 @@ def domain_select(cnt: torch.Tensor, dom_keys: torch.Tensor,
     return out
 
 
+def collapse_m_max() -> int:
+    """The largest per-domain cap m (COLLAPSE_M_MAX)."""
+    return int(_ext.lib().infomesh_collapse_m_max())
+
+
+def collapse_k_max() -> int:
+    """The largest k collapse_select takes."""
+    return int(_ext.lib().infomesh_collapse_k_max())
+
+
+def collapse_chunk_docs() -> int:
+    """Documents per workgroup of domain_best (COLLAPSE_CHUNK)."""
+    return int(_ext.lib().infomesh_collapse_chunk_docs())
+
+
+def collapse_lds_slots() -> int:
+    """Slots of domain_best's per-workgroup LDS table."""
+    return int(_ext.lib().infomesh_collapse_lds_slots())
+
+
+def domain_best(scores: torch.Tensor, rows: torch.Tensor,
+                dom_id: torch.Tensor, D: int, m: int, positive: bool,
+                mask: torch.Tensor | None = None,
+                row_pred: torch.Tensor | None = None,
+                out: torch.Tensor | None = None,
+                rows_device: torch.Tensor | None = None) -> torch.Tensor:
+    """The m best eligible documents of every domain id, as order keys
+    (csrc/collapse.hip, where the key and the order are written down):
+    scores [B, N] f32, dom_id [N] i32 with every entry in [0, D) and,
+    with a mask, mask [P, W] i32 + row_pred [B] i32, on the device.
+    positive: the BM25 form, eligible = passes the mask and score > 0
+    (facet_counts' rule); else the dense form, eligible = passes the
+    mask. rows [R] i32 names the batch rows and is checked here, on the
+    host, before any launch (a host tensor is uploaded, a device tensor
+    copied back). rows_device: the device copy of a host `rows`, from a
+    caller that has uploaded it already. out: a contiguous [m, R, D] i64
+    device tensor to fill; it is zeroed here. Returns best [m, R, D] i64 holding the u64 keys'
+    bits: best[j, r, i] is the (j+1)-th largest key of domain i in row
+    rows[r], 0 when the domain has no such document. m outside
+    1 .. collapse_m_max() is a ValueError, and nothing is launched."""
+    _check(scores, torch.float32, "scores")
+    _check(dom_id, torch.int32, "dom_id")
+    assert scores.dim() == 2
+    B, N = scores.shape
+    if not 1 <= m <= collapse_m_max():
+        raise ValueError(
+            f"domain_best: m = {m}; 1 <= m <= {collapse_m_max()}")
+    if D < 1:
+        raise ValueError(f"domain_best: D = {D}; at least one domain")
+    assert 1 <= N < 2 ** 31 and dom_id.shape == (N,), "dom_id: [N]"
+    assert (mask is None) == (row_pred is None), \
+        "mask and row_pred go together"
+    W = P = 0
+    if mask is not None:
+        _check(mask, torch.int32, "mask")
+        _check(row_pred, torch.int32, "row_pred")
+        assert mask.dim() == 2 and mask.shape[1] * 32 >= N
+        assert row_pred.numel() == B
+        P, W = mask.shape
+    h_rows = _host_words(rows, "rows")
+    assert h_rows.dim() == 1 and h_rows.numel() >= 1, "rows: [R], R >= 1"
+    R = h_rows.numel()
+    assert bool(((h_rows >= 0) & (h_rows < B)).all()), \
+        "rows points outside the batch"
+    if (N + collapse_chunk_docs() - 1) // collapse_chunk_docs() > 65535:
+        raise ValueError(f"domain_best: N = {N}; more than 65535 chunks")
+    dev = scores.device
+    if rows_device is not None:
+        assert not rows.is_cuda and rows_device.is_cuda \
+            and rows_device.dtype == torch.int32 \
+            and rows_device.shape == rows.shape, "rows_device: rows, uploaded"
+        rows_d = rows_device
+    else:
+        rows_d = rows if rows.is_cuda else rows.to(dev, non_blocking=True)
+    if out is None:
+        out = torch.zeros((m, R, D), device=dev, dtype=torch.int64)
+    else:
+        _check(out, torch.int64, "out")
+        assert out.shape == (m, R, D), "out: [m, R, D]"
+        out.zero_()
+    _ext.lib().infomesh_domain_best(
+        scores.data_ptr(), rows_d.data_ptr(), _ptr(mask), _ptr(row_pred),
+        dom_id.data_ptr(), out.data_ptr(), B, R, N, W, P, D, m,
+        1 if positive else 0, _ext.stream_ptr())
+    return out
+
+
+def collapse_select(best: torch.Tensor, k: int
+                    ) -> tuple[torch.Tensor, torch.Tensor]:
+    """The first k documents of every row's capped set, in key order
+    (csrc/collapse.hip): best [m, R, D] i64 as domain_best returns it ->
+    (vals [R, k] f32, idx [R, k] i32), padded with -inf / -1. k outside
+    1 .. collapse_k_max() is a ValueError, and nothing is launched."""
+    _check(best, torch.int64, "best")
+    assert best.dim() == 3
+    m, R, D = best.shape
+    if not 1 <= m <= collapse_m_max():
+        raise ValueError(
+            f"collapse_select: m = {m}; 1 <= m <= {collapse_m_max()}")
+    if not 1 <= k <= collapse_k_max():
+        raise ValueError(
+            f"collapse_select: k = {k}; 1 <= k <= {collapse_k_max()}")
+    assert R >= 1 and D >= 1, "best: [m, R, D]"
+    vals = torch.empty((R, k), device=best.device, dtype=torch.float32)
+    idx = torch.empty((R, k), device=best.device, dtype=torch.int32)
+    _ext.lib().infomesh_collapse_select(
+        best.data_ptr(), vals.data_ptr(), idx.data_ptr(), R, D, m, k,
+        _ext.stream_ptr())
+    return vals, idx
+
+
 def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
                qt_off: torch.Tensor, qt_ut: torch.Tensor,
                qt_idf: torch.Tensor, u_begin: torch.Tensor,

@@ -317,6 +317,57 @@ def domain_top(scores: torch.Tensor, rows: torch.Tensor,
         [int(b) for b in rows.cpu().numpy()], K))
 
 
+def collapse_topk(scores: torch.Tensor, rows: torch.Tensor,
+                  dom_id: torch.Tensor, m: int, k: int, positive: bool,
+                  mask: torch.Tensor | None = None,
+                  row_pred: torch.Tensor | None = None
+                  ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Oracle of csrc/collapse.hip (domain_best x m, then
+    collapse_select), by sorting and counting: per batch row rows[r],
+    the eligible documents (they pass the mask; positive: and score > 0)
+    sorted by ordered_key(score) descending, then column ascending; a
+    document stays if fewer than m documents of its dom_id stand before
+    it; the first k of those, padded with -inf / -1.
+    -> (vals [R, k] f32, idx [R, k] i32)."""
+    s = scores.detach().float().cpu()
+    return collapse_topk_rows(
+        s, _fail_rows(mask, row_pred, s.shape[1]), dom_id,
+        [int(b) for b in rows.cpu().numpy()], m, k, positive)
+
+
+def collapse_topk_rows(s: torch.Tensor, fail, dom_id: torch.Tensor,
+                       rows: list[int], m: int, k: int, positive: bool
+                       ) -> tuple[torch.Tensor, torch.Tensor]:
+    """collapse_topk with the mask unpacked: s [B, N] f32 on the host,
+    fail bool [B, N] (numpy, True where a document fails its row's mask)
+    or None. CpuShard calls this with the fail rows it has."""
+    import numpy as np
+    okey = ordered_key(s).numpy()
+    s = s.numpy()
+    N = s.shape[1]
+    dom = dom_id.cpu().numpy().astype(np.int64)
+    R = len(rows)
+    vals = np.full((R, k), -np.inf, dtype=np.float32)
+    idx = np.full((R, k), -1, dtype=np.int32)
+    for r, b in enumerate(rows):
+        ok = s[b] > 0 if positive else np.ones(N, dtype=bool)
+        if fail is not None:
+            ok = ok & ~fail[b]
+        cols = np.nonzero(ok)[0]
+        cols = cols[np.lexsort((cols, -okey[b, cols]))]
+        # rank within the domain: group the ordered list by domain,
+        # stably, and count from each group's start
+        d = dom[cols]
+        by_dom = np.argsort(d, kind="stable")
+        ds = d[by_dom]
+        rank = np.empty(len(cols), dtype=np.int64)
+        rank[by_dom] = np.arange(len(cols)) - np.searchsorted(ds, ds)
+        keep = cols[rank < m][:k]
+        vals[r, :len(keep)] = s[b, keep]
+        idx[r, :len(keep)] = keep
+    return torch.from_numpy(vals), torch.from_numpy(idx)
+
+
 def masked_topk(scores: torch.Tensor, k: int, bits: torch.Tensor,
                 row_pred: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Oracle of the masked top-k: failing columns become -inf, then

@@ -21,7 +21,7 @@ import torch
 from ..index.doc_attrs import (HAS_ALLOW_BIT, HAS_BLOCK_BIT, TOP_FETCH,
                                U32_MAX, FacetSpec, PackedFacets, TermOps,
                                pack_facets, pack_pred_sets)
-from ..index.gpu_index import GpuShard, ShardHits
+from ..index.gpu_index import GpuShard, ShardHits, per_domain_caps
 from .fabric import Fabric
 
 RRF_K = 60
@@ -40,6 +40,11 @@ _HAS_LISTS = HAS_ALLOW_BIT | HAS_BLOCK_BIT
 # stripped before the predicates are unpacked, and only such a batch is
 # followed by the two broadcasts of _broadcast_facets.
 _HAS_FACETS = 1 << 20
+# Bits 21..23 of a row's z hold its per-domain cap m (0 = none, at most
+# COLLAPSE_M_MAX = 4). They are stripped before the predicates are
+# unpacked; an uncapped batch's broadcast is what it always was.
+_CAP_SHIFT = 21
+_CAP_BITS = 7 << _CAP_SHIFT
 # Bit 40 of the hash count in _broadcast_facets' header: the spec asks
 # for top domains somewhere, and its body carries one T per counted row.
 _HAS_TOP = 1 << 40
@@ -216,6 +221,69 @@ def rrf_fuse(ids_lists: list[torch.Tensor], score_lists: list[torch.Tensor],
     return out_ids, out_scores
 
 
+def cap_per_domain(ids: torch.Tensor, scores: torch.Tensor,
+                   doms: torch.Tensor, m_row: torch.Tensor, n: int
+                   ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """At most m_row[b] entries per domain in every row of a hit list,
+    pure torch: ids [B, M] i64 (-1 = pad), scores [B, M] f32, doms
+    [B, M] the entries' domain words (any integer dtype, compared as
+    they are), m_row [B] integer, 0 = no cap. Each row is sorted by
+    score descending, then id ascending; an entry whose rank among the
+    entries of its domain is >= m is dropped; the first n of the rest
+    are returned as (ids, scores, doms) [B, min(n, M)], padded with
+    -1 / -inf / 0. Ids are unique within a row (a document lives in one
+    shard)."""
+    B, M = ids.shape
+    dev = ids.device
+    pad = ids < 0
+    # three stable sorts, least significant key first: id, score, pad
+    order = torch.sort(ids, dim=1, stable=True).indices
+    s = torch.gather(scores, 1, order)
+    o2 = torch.sort(s, dim=1, descending=True, stable=True).indices
+    order = torch.gather(order, 1, o2)
+    o3 = torch.sort(torch.gather(pad, 1, order).to(torch.int8), dim=1,
+                    stable=True).indices
+    order = torch.gather(order, 1, o3)
+    ids = torch.gather(ids, 1, order)
+    scores = torch.gather(scores, 1, order)
+    doms = torch.gather(doms, 1, order)
+    pad = ids < 0
+    # rank within the domain: group each row by domain, stably, and
+    # count from the group's start (pads sort last, so they stand behind
+    # every real entry of a domain that shares their word)
+    ds, by_dom = torch.sort(doms, dim=1, stable=True)
+    pos = torch.arange(M, device=dev).expand(B, M)
+    start = torch.zeros_like(pos)
+    start[:, 1:] = torch.where(ds[:, 1:] != ds[:, :-1], pos[:, 1:],
+                               torch.zeros_like(pos[:, 1:]))
+    start = torch.cummax(start, dim=1).values
+    rank = torch.empty_like(pos).scatter_(1, by_dom, pos - start)
+    m = m_row.to(dev).long().reshape(B, 1)
+    keep = ~pad & ((m == 0) | (rank < m))
+    front = torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices
+    front = front[:, :min(n, M)]
+    keep = torch.gather(keep, 1, front)
+    ids = torch.where(keep, torch.gather(ids, 1, front),
+                      torch.full_like(front, -1))
+    scores = torch.gather(scores, 1, front)
+    scores = torch.where(keep, scores,
+                         torch.full_like(scores, -float("inf")))
+    doms = torch.gather(doms, 1, front)
+    return ids, scores, torch.where(keep, doms, torch.zeros_like(doms))
+
+
+def lookup_domains(ids: torch.Tensor, pair_ids: torch.Tensor,
+                   pair_doms: torch.Tensor) -> torch.Tensor:
+    """The domain words of ids [B, n] (-1 = pad) from the row's
+    (id, domain) pairs pair_ids / pair_doms [B, M]; every real id is
+    among its row's pairs. 0 at padding."""
+    ps, order = torch.sort(pair_ids, dim=1)
+    pd = torch.gather(pair_doms, 1, order)
+    at = torch.searchsorted(ps, ids.clamp(min=0).contiguous())
+    d = torch.gather(pd, 1, at.clamp(max=ps.shape[1] - 1))
+    return torch.where(ids >= 0, d, torch.zeros_like(d))
+
+
 def _as_i64(sl: torch.Tensor) -> torch.Tensor:
     """Bit-cast a float32 id slice back to int64 [..., 2k] -> [..., k],
     robust to storage offset/stride parity (a contiguous slice keeps
@@ -256,12 +324,23 @@ class DistributedQueryPlane:
                      encode_shard=None,
                      filters: list | None = None,
                      term_ops: list | None = None,
-                     facets: FacetSpec | None = None) -> FusedHits | None:
+                     facets: FacetSpec | None = None,
+                     per_domain: list | None = None) -> FusedHits | None:
         """filters (rank 0): one DocFilter or None per row; every shard
         applies them in its top-k selection. term_ops (rank 0): one
         TermOps or None per row, honoured by every shard alike. facets
         (rank 0): a FacetSpec; every shard counts its matching documents
         for the rows it names and FusedHits.facets holds the sums.
+        per_domain (rank 0): one int or None per row; a row with a
+        cap m, 1 <= m <= 4, gets at most m hits per domain: every shard
+        caps both planes over its whole score row
+        (ops/csrc/collapse.hip), the gathered lists are capped again per
+        plane (exact up to exchange of equal scores, as the plain top-k
+        is at rank k), RRF-fused to the full candidate width, and the
+        fused list is capped once more before the cut to n_results.
+        Domains compare by 32-bit hash: a collision can only
+        over-collapse. A capped batch fuses uncaptured and does one more
+        all-gather; every other batch is served as it always was.
 
         Collective search with rank-fault tolerance: on a collective
         failure (dead rank → timeout) the fabric shrinks to the
@@ -273,11 +352,13 @@ class DistributedQueryPlane:
             # ValueError on rank 0 alone, with nothing sent; the retry
             # below carries the packed spec along
             facets = pack_facets(facets, B)
+        # checked before any collective as well: a ValueError on rank 0
+        per_domain = per_domain_caps(per_domain, B)
         try:
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
                                       encode_fn, encode_shard, filters,
-                                      term_ops, facets)
+                                      term_ops, facets, per_domain)
         except RuntimeError as e:
             if not self.fabric.initialized or not self.fabric.collective_ok:
                 raise
@@ -311,7 +392,7 @@ class DistributedQueryPlane:
             return self._search_batch(queries_terms, query_emb, B, dim,
                                       n_results, use_dense, phase_t,
                                       encode_fn, encode_shard, filters,
-                                      term_ops, facets)
+                                      term_ops, facets, per_domain)
 
     def _sharded_encode(self, encode_shard: dict, B: int,
                         dim: int) -> torch.Tensor:
@@ -351,7 +432,8 @@ class DistributedQueryPlane:
                       use_dense: bool = True,
                       phase_t: dict | None = None,
                       encode_fn=None, encode_shard=None, filters=None,
-                      term_ops=None, facets=None) -> FusedHits | None:
+                      term_ops=None, facets=None,
+                      per_domain=None) -> FusedHits | None:
         """One collective search attempt. Rank 0 passes real queries and
         gets the FusedHits; other ranks pass None and get None.
 
@@ -379,11 +461,13 @@ class DistributedQueryPlane:
                                            encode_shard=encode_shard,
                                            filters=filters,
                                            term_ops=term_ops,
-                                           facets=facets)
+                                           facets=facets,
+                                           per_domain=per_domain)
             tp = mark("plane.shard", tp)
         else:
-            terms, filters, term_ops, facets = self._broadcast_query(
-                queries_terms, B, filters, term_ops, facets)
+            terms, filters, term_ops, facets, per_domain = \
+                self._broadcast_batch(queries_terms, B, filters, term_ops,
+                                      facets, per_domain)
             if encode_shard is not None:
                 emb = self._sharded_encode(encode_shard, B, dim).float()
             else:
@@ -398,7 +482,8 @@ class DistributedQueryPlane:
             hits = self.shard.search(
                 terms, emb if use_dense else None, k=self.k,
                 scores_buf=self._get_scores_buf(B), phase_t=phase_t,
-                filters=filters, term_ops=term_ops, facets=facets)
+                filters=filters, term_ops=term_ops, facets=facets,
+                per_domain=per_domain)
             tp = mark("plane.shard", tp)
         # ONE packed all-gather instead of four: xGMI collectives at
         # this payload size (a few hundred KB) are latency-dominated,
@@ -433,6 +518,14 @@ class DistributedQueryPlane:
             # rank holds the same spec and takes the branch
             top_reports = self.fabric.all_gather(
                 hits.dom_top.to(self.fabric.device).contiguous())
+        hit_doms = None
+        if hits.bm25_dom is not None:
+            # a capped batch: the hits' domain words, both planes in one
+            # more all-gather (every rank read the same caps from the
+            # terms broadcast and takes the branch)
+            hit_doms = self.fabric.all_gather(torch.cat(
+                [hits.bm25_dom, hits.dense_dom], dim=1)
+                .to(self.fabric.device).contiguous())      # [W, B, 2k]
         tp = mark("plane.gather", tp)
         top_merged = None
         if top_reports is not None:
@@ -452,7 +545,14 @@ class DistributedQueryPlane:
         bm_i = bm_i.permute(1, 0, 2).reshape(B, W * k)
         dn_s = dn_s.permute(1, 0, 2).reshape(B, W * k)
         dn_i = dn_i.permute(1, 0, 2).reshape(B, W * k)
-        if use_dense:
+        if hit_doms is not None:
+            ids, scores, (bm_i, bm_s), (dn_i, dn_s) = self._fuse_capped(
+                bm_i, bm_s, dn_i, dn_s,
+                hit_doms.permute(1, 0, 2)[:, :, :k].reshape(B, W * k),
+                hit_doms.permute(1, 0, 2)[:, :, k:].reshape(B, W * k),
+                torch.tensor(self._caps, device=bm_i.device), n_results,
+                use_dense)
+        elif use_dense:
             if bm_i.is_cuda:
                 gf = self._fuse_graphs.get(n_results)
                 if gf is None:
@@ -480,10 +580,57 @@ class DistributedQueryPlane:
                          degraded=self.fabric.degraded, facets=facet_sum,
                          top_domains=top_domains)
 
+    @staticmethod
+    def _fuse_capped(bm_i, bm_s, dn_i, dn_s, bm_d, dn_d, m_row, n_results,
+                     use_dense):
+        """The fused result of a batch with capped rows (rank 0): cap
+        each plane's gathered list, RRF-fuse to the full candidate
+        width, cap the fused list, cut to n_results. -> (ids, scores,
+        (bm25 ids, scores), (dense ids, scores)), a capped row's plane
+        lists as capped and sorted."""
+        M = bm_i.shape[1]
+        # an uncapped row keeps its lists as gathered, so that the order
+        # among its equal scores, and with it the fused list, is what an
+        # uncapped batch gives it
+        free = (m_row == 0).reshape(-1, 1)
+
+        def capped(i, s, d):
+            ci, cs, cd = cap_per_domain(i, s, d, m_row, M)
+            return (torch.where(free, i, ci), torch.where(free, s, cs),
+                    torch.where(free, d, cd))
+        bm_i, bm_s, bm_d = capped(bm_i, bm_s, bm_d)
+        dn_i, dn_s, dn_d = capped(dn_i, dn_s, dn_d)
+        if not use_dense:
+            # a capped row is sorted already; a free one as always
+            order = torch.argsort(bm_s, dim=1, descending=True)
+            order = torch.where(free, order,
+                                torch.arange(M, device=order.device)
+                                .expand_as(order))[:, :n_results]
+            return (torch.gather(bm_i, 1, order),
+                    torch.gather(bm_s, 1, order), (bm_i, bm_s),
+                    (dn_i, dn_s))
+        ids, scores = rrf_fuse([bm_i, dn_i], [bm_s, dn_s], [1.0, 1.0],
+                               2 * M)
+        doms = lookup_domains(ids, torch.cat([bm_i, dn_i], dim=1),
+                              torch.cat([bm_d, dn_d], dim=1))
+        c_ids, c_scores, _ = cap_per_domain(ids, scores, doms, m_row,
+                                            n_results)
+        # padding carries score 0 in a fused list, as rrf_fuse pads
+        c_scores = torch.clamp(c_scores, min=0.0)
+        # a free row is fused as an uncapped batch fuses it, to n_results:
+        # the order among equal fused scores depends on the width asked
+        # for
+        p_ids, p_scores = rrf_fuse([bm_i, dn_i], [bm_s, dn_s], [1.0, 1.0],
+                                   n_results)
+        return (torch.where(free, p_ids, c_ids),
+                torch.where(free, p_scores, c_scores), (bm_i, bm_s),
+                (dn_i, dn_s))
+
     def _search_overlapped(self, queries_terms, query_emb, encode_fn,
                            B, dim, use_dense, phase_t=None,
                            encode_shard=None, filters=None,
-                           term_ops=None, facets=None) -> ShardHits:
+                           term_ops=None, facets=None,
+                           per_domain=None) -> ShardHits:
         """BM25 on a side stream || query encoding on the main stream.
 
         Broadcast order (terms, then embeddings) is identical on all
@@ -506,8 +653,9 @@ class DistributedQueryPlane:
             self._bm25_stream = torch.cuda.Stream(dev)
         # terms must be broadcast before any rank's shard work
         tp = _time.perf_counter()
-        terms, filters, term_ops, facets = self._broadcast_query(
-            queries_terms, B, filters, term_ops, facets)
+        terms, filters, term_ops, facets, per_domain = \
+            self._broadcast_batch(queries_terms, B, filters, term_ops,
+                                  facets, per_domain)
         tp = mark("ov.terms", tp)
         main = torch.cuda.current_stream(dev)
         mask = None
@@ -517,13 +665,18 @@ class DistributedQueryPlane:
             mask = self.shard._mask_for(filters, B, term_ops)
             for t in mask or ():
                 t.record_stream(self._bm25_stream)
+        if per_domain is not None:
+            # both planes read the epoch's domain tables, on two streams:
+            # build them here, before the side stream branches off
+            self.shard._domain_tables()
         self._bm25_stream.wait_stream(main)
         counts = dom_top = tally = None
+        doms = {}
         with torch.cuda.stream(self._bm25_stream):
             if facets is None:
                 bm_vals, bm_idx = self.shard.search_bm25(
                     terms, self.k, scores_buf=self._get_scores_buf(B),
-                    filters=filters, _mask=mask)
+                    filters=filters, _mask=mask, per_domain=per_domain)
             else:
                 # the counts ride the side stream with the scores they
                 # read; main waits for that stream before the gathers
@@ -531,8 +684,10 @@ class DistributedQueryPlane:
                     self.shard.search_bm25_top(
                         terms, self.k, facets,
                         scores_buf=self._get_scores_buf(B), filters=filters,
-                        _mask=mask)
+                        _mask=mask, per_domain=per_domain)
             bm_ids = self.shard.to_global(bm_idx)
+            if per_domain is not None:
+                doms["bm25_dom"] = self.shard.hit_domains(bm_idx)
         tp = mark("ov.bm25", tp)
         if encode_shard is not None:
             emb_t = self._sharded_encode(encode_shard, B, dim).float()
@@ -548,17 +703,24 @@ class DistributedQueryPlane:
         if use_dense and self.shard.embeddings is not None:
             dn_vals, dn_idx = self.shard.search_dense(emb_t, self.k,
                                                       filters=filters,
-                                                      _mask=mask)
+                                                      _mask=mask,
+                                                      per_domain=per_domain)
             dn_ids = self.shard.to_global(dn_idx)
+            if per_domain is not None:
+                doms["dense_dom"] = self.shard.hit_domains(dn_idx)
             tp = mark("ov.dense", tp)
         else:
             k = min(self.k, self.shard.n_docs)
             dn_vals = torch.full((B, k), -float("inf"), device=dev)
             dn_ids = torch.full((B, k), -1, device=dev, dtype=torch.int64)
+            if per_domain is not None:
+                doms["dense_dom"] = torch.zeros((B, k), device=dev,
+                                                dtype=torch.int32)
         main.wait_stream(self._bm25_stream)
         return ShardHits(bm25_scores=bm_vals, bm25_ids=bm_ids,
                          dense_scores=dn_vals, dense_ids=dn_ids,
-                         facets=counts, dom_top=dom_top, dom_tally=tally)
+                         facets=counts, dom_top=dom_top, dom_tally=tally,
+                         **doms)
 
     def _broadcast_terms(self, queries_terms, B, filters=None):
         """-> (terms, filters) of a batch without term operands."""
@@ -566,22 +728,34 @@ class DistributedQueryPlane:
 
     def _broadcast_query(self, queries_terms, B, filters=None,
                          term_ops=None, facets=None):
-        """-> (terms, filters, term_ops, facets) as every rank must see
-        them. At world > 1 the predicates ride in the one terms broadcast
+        """_broadcast_batch of a batch without per-domain caps:
+        -> (terms, filters, term_ops, facets)."""
+        return self._broadcast_batch(queries_terms, B, filters, term_ops,
+                                     facets)[:4]
+
+    def _broadcast_batch(self, queries_terms, B, filters=None,
+                         term_ops=None, facets=None, per_domain=None):
+        """-> (terms, filters, term_ops, facets, per_domain) as every
+        rank must see them. At world > 1 the predicates ride in the one terms broadcast
         (packed words, which the shards accept in place of DocFilter
         objects), and so do the term operands, as flag bits on the term
         entries (pack_term_row). term_ops comes back None when no row
         has an operand. facets (rank 0: a FacetSpec or PackedFacets)
         comes back as PackedFacets, or None when no row is counted; the
         terms broadcast only announces it (_HAS_FACETS), the spec itself
-        follows in _broadcast_facets."""
+        follows in _broadcast_facets. per_domain (rank 0: one cap per
+        row, or None) rides in bits 21..23 of the row's z word and comes
+        back as a list of ints, or None when no row is capped; it is
+        kept in self._caps for the fusion on rank 0."""
         if term_ops is not None and not any(term_ops):
             term_ops = None
         facets = pack_facets(facets, B)
+        per_domain = per_domain_caps(per_domain, B)
+        self._caps = per_domain
         if self.fabric.world == 1 and queries_terms is not None:
             # no collective needed: skip the pack + GPU round-trip +
             # device sync entirely
-            return queries_terms, filters, term_ops, facets
+            return queries_terms, filters, term_ops, facets, per_domain
         dev = self.fabric.device
         T = MAX_QUERY_TERMS
         terms_t = torch.full((B, T + _PRED_COLS), -1, dtype=torch.int64)
@@ -603,6 +777,8 @@ class DistributedQueryPlane:
                 terms_t[:, T:] = torch.from_numpy(cols.view(np.int64))
             if facets is not None:
                 terms_t[0, T + 1] |= _HAS_FACETS
+            if per_domain is not None:
+                terms_t[:, T + 1] |= torch.tensor(per_domain) << _CAP_SHIFT
         terms_t = terms_t.to(dev)
         self.fabric.broadcast(terms_t)
         tt = terms_t.cpu().numpy()
@@ -611,6 +787,9 @@ class DistributedQueryPlane:
         # unpacked: row 0 keeps its own words, filtered or not
         has_facets = bool(cols[0, 1] & np.uint64(_HAS_FACETS))
         cols[0, 1] &= ~np.uint64(_HAS_FACETS)
+        caps = ((cols[:, 1] & np.uint64(_CAP_BITS)) >> np.uint64(_CAP_SHIFT))
+        cols[:, 1] &= ~np.uint64(_CAP_BITS)
+        self._caps = [int(c) for c in caps] if caps.any() else None
         if has_facets:
             facets = self._broadcast_facets(facets)
         has = (cols[:, 1] & np.uint64(_HAS_FILTER)) != 0
@@ -629,7 +808,7 @@ class DistributedQueryPlane:
         term_ops = [ops for _, ops in rows]
         return ([terms for terms, _ in rows], filters,
                 term_ops if any(term_ops) else None,
-                facets if has_facets else None)
+                facets if has_facets else None, self._caps)
 
     def _broadcast_facets(self, packed: PackedFacets | None) -> PackedFacets:
         """The spec of a batch whose terms broadcast announced one, in

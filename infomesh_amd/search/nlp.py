@@ -310,6 +310,47 @@ def parse_facet_token(query: str) -> tuple[str, tuple[str, ...] | None]:
     return parse_facet_request(query)[:2]
 
 
+# A per-domain cap travels as one token of the query text, like the
+# filters do: persite:N, at most N hits per site, 1 <= N <= PERSITE_MAX
+# (the GPU plane's COLLAPSE_M_MAX). No other code reads or writes this
+# syntax.
+PERSITE_MAX = 4
+_PERSITE_RE = re.compile(r"(?<!\S)persite:(\d+)(?!\S)")
+
+
+def with_persite_token(query: str, m: int = 0) -> str:
+    """`query` with the token appended that parse_persite_token reads
+    back; m = 0 (or None) appends nothing. m outside 0 .. PERSITE_MAX is
+    a ValueError."""
+    m = int(m or 0)
+    if not 0 <= m <= PERSITE_MAX:
+        raise ValueError(f"per_domain = {m}; 0 (no cap) or 1 .. {PERSITE_MAX}")
+    return f"{query} persite:{m}".lstrip() if m else query
+
+
+def parse_persite_token(query: str, clamp: bool = False
+                        ) -> tuple[str, int]:
+    """(text without the token, cap) of a query with a persite:N token;
+    (query, 0) when it carries none; the last one counts. N outside
+    1 .. PERSITE_MAX is a ValueError, so that a typed token fails its
+    caller; clamp=True (the batch executor, where an error would fail
+    every caller of the batch) brings N into the range instead."""
+    found: list[int] = []
+
+    def _sub(m: re.Match) -> str:
+        found.append(int(m.group(1)))
+        return ""
+    text = _PERSITE_RE.sub(_sub, query)
+    if not found:
+        return query, 0
+    n = found[-1]
+    if not 1 <= n <= PERSITE_MAX:
+        if not clamp:
+            raise ValueError(f"persite:{n}; 1 <= N <= {PERSITE_MAX}")
+        n = min(max(n, 1), PERSITE_MAX)
+    return re.sub(r"\s{2,}", " ", text).strip(), n
+
+
 # ---------------------------------------------------- related searches
 
 @dataclass

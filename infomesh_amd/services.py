@@ -28,16 +28,17 @@ from .errors import GpuExtensionMissing, InfoMeshError
 from .crawler.lang_detect import known_languages
 from .index.doc_attrs import (FACET_MAX_DOMS, TOP_DOMAINS_MAX, DocFilter,
                               FacetCounts, FacetSpec, pack_pred_sets)
-from .index.gpu_index import bm25_term_ids
+from .index.gpu_index import bm25_term_ids, per_domain_caps
 from .index.link_graph import LinkGraph
 from .index.local_store import Document, LocalStore
 from .search.batcher import QueryBatcher
 from .search.cache import QueryCache
 from .search.facets import compute_facets
 from .search.nlp import (RelatedSearchTracker, parse_facet_request,
-                         parse_facet_token, parse_query_filters,
-                         parse_term_operators, with_facet_request,
-                         with_filter_tokens)
+                         parse_facet_token, parse_persite_token,
+                         parse_query_filters, parse_term_operators,
+                         with_facet_request, with_filter_tokens,
+                         with_persite_token)
 from .search.passage import fast_snippet
 from .search.query import (SearchResponse, preprocess_query,
                            search_hybrid, search_local)
@@ -301,7 +302,8 @@ class AppContext:
                deduct: bool = True, include_domains=None,
                exclude_domains=None,
                recency_days: float = 0, facets: bool = False,
-               facet_domains=(), top_domains: int = 0) -> SearchResponse:
+               facet_domains=(), top_domains: int = 0,
+               per_domain: int = 0) -> SearchResponse:
         """Unified search entry (reference mcp/handlers.py:382 flow):
         cache -> credits -> local/hybrid/distributed -> cache.
 
@@ -333,9 +335,28 @@ class AppContext:
         names are surely the true first T; when it is False a domain
         that is not shown may hold up to "top_domains_bound" matches.
         A hash whose name is unknown reads "#%08x". Served from FTS it
-        is the hits' most common T domains, without those two keys."""
+        is the hits' most common T domains, without those two keys.
+
+        per_domain: m > 0 returns at most m hits per site, 1 <= m <= 4;
+        a persite:N token typed into the query asks for the same, and
+        the parameter wins. Outside the range is a ValueError, here, on
+        the caller's thread. Served by the engine, the cap is exact over
+        the whole match set: every shard picks each site's best m on
+        both planes, and the fused list is capped again, so up to
+        `limit` hits of different sites come back. Sites compare by
+        32-bit hash there: two sites whose hashes collide share one cap.
+        Served from FTS, the hit list is thinned by quality.diversify's
+        greedy rule, with the hits over the cap dropped: the cap then
+        covers the returned hits only, which can leave fewer than
+        `limit`."""
         from .utils.plugins import GLOBAL_PLUGINS
         query = GLOBAL_PLUGINS.run("pre_search", query, mode=mode)
+        # persite:N is split off on the caller's thread (a bad N fails
+        # this caller alone); _engine_search writes it back for the
+        # batch, the FTS paths never see it
+        query, typed = parse_persite_token(query)
+        cap = int(per_domain or 0) or typed
+        per_domain_caps([cap], 1)           # out of range: a ValueError
         # facets:@... is the serving path's own syntax (_engine_search
         # writes it, _batch_execute reads it): one typed into the query
         # is dropped here, on the caller's thread, so that it neither
@@ -368,7 +389,8 @@ class AppContext:
         key = QueryCache.make_key(query, limit=limit, mode=mode,
                                   facets=None if fdoms is None
                                   else list(fdoms),
-                                  top_domains=top or None)
+                                  top_domains=top or None,
+                                  per_domain=cap or None)
         if use_cache:
             cached = self.cache.get(key)
             if cached is not None:
@@ -408,7 +430,8 @@ class AppContext:
                 # LocalStore (round-1 double-fusion fix)
                 resp = self._engine_search(query, limit, mode,
                                            facet_domains=fdoms,
-                                           top_domains=top)
+                                           top_domains=top, per_domain=cap)
+                cap = 0
             else:
                 resp = search_hybrid(
                     self.store, None, query, limit=limit,
@@ -421,6 +444,17 @@ class AppContext:
                     resp.mode = "distributed"
         else:
             raise InfoMeshError("SRCH001", f"unknown mode {mode!r}")
+        if cap:
+            # FTS served it: the cap can only thin out the hits it got
+            # (quality.diversify's greedy pass, without the tail it
+            # keeps: hits over the cap are dropped, not moved back)
+            seen: Counter = Counter()
+            kept = []
+            for r in resp.results:
+                seen[r.domain] += 1
+                if seen[r.domain] <= cap:
+                    kept.append(r)
+            resp.results = kept
         if fdoms is not None and resp.facets is None:
             # FTS served it: SQLite hands back a LIMITed list, so the
             # counts can only cover the hits
@@ -496,7 +530,11 @@ class AppContext:
             asked.append((text,
                           doms if doms is None else doms[:FACET_MAX_DOMS]))
             tops.append(min(top, TOP_DOMAINS_MAX) if doms is not None else 0)
-        queries = [text for text, _ in asked]
+        # the per-site cap is a token as well (nlp.with_persite_token);
+        # one out of range is clamped here, never raised
+        capped = [parse_persite_token(text, clamp=True) for text, _ in asked]
+        queries = [text for text, _ in capped]
+        caps = [m for _, m in capped]
         spec = None
         if any(doms is not None for _, doms in asked):
             now = math.floor(time.time())
@@ -535,6 +573,8 @@ class AppContext:
                       exclude=[exc for _, _, exc in split])
         else:
             kw = {}
+        if any(caps):
+            kw["per_domain"] = caps
         counts: list = [None] * len(queries)
         if spec is None:
             per_q = self.engine.search_many(queries, limit=limit,
@@ -611,11 +651,13 @@ class AppContext:
 
     def _engine_search(self, query: str, limit: int, mode: str,
                        facet_domains=None,
-                       top_domains: int = 0) -> SearchResponse:
+                       top_domains: int = 0,
+                       per_domain: int = 0) -> SearchResponse:
         """GPU-plane search via the micro-batcher (fused once on the
         plane, hydrated batch-wide in _batch_execute). facet_domains:
         None, or the domains to count of a request with facets;
-        top_domains: how many top domains such a request asks for."""
+        top_domains: how many top domains such a request asks for;
+        per_domain: the per-site cap, 0 for none."""
         t0 = time.time()
         trace = None
         if self.otlp is not None and self.otlp.enabled:
@@ -638,8 +680,11 @@ class AppContext:
         # token through untouched, which is why AppContext.search drops
         # a typed one first; one that still came this way goes here.
         eff = parse_facet_token(eff)[0]
-        sent = eff if facet_domains is None \
-            else with_facet_request(eff, facet_domains, top_domains)
+        # likewise the per-site token: written here alone
+        eff = parse_persite_token(eff, clamp=True)[0]
+        sent = with_persite_token(eff, per_domain)
+        sent = sent if facet_domains is None \
+            else with_facet_request(sent, facet_domains, top_domains)
         batcher = self.ensure_batcher()
         if trace is not None:
             with trace.span("engine"):
