@@ -73,19 +73,64 @@ def init_bert_weights(cfg: BertConfig, seed: int = 1234,
     return out
 
 
+# The fast path's items, each of which leaves the bits of the plain
+# kernel sequence unchanged:
+#   merge  attention writes the merged [B*S, H] layout (no merge_heads)
+#   short  attention may pick its short 32x32 tile
+#   tail   cls_only runs the last layer's back half on the CLS rows only
+#   embed  the embedding front is one kernel
+FAST_ITEMS = frozenset({"merge", "short", "tail", "embed"})
+
+
+def cls_tail_gemms(H: int, F: int) -> tuple[tuple[int, int], ...]:
+    """(N, K) of the tail's three GEMMs: attn_out, ffn_in, ffn_out."""
+    return ((H, H), (F, H), (H, F))
+
+
+def cls_tail_routes_match(B: int, rows: int, H: int, F: int) -> bool:
+    """Route half of the same-kernel rule: the tail's GEMMs at M = B and
+    the full layer's at M = rows both run the gemm.hip family."""
+    return all(K.gemm_route(B, N, Kd, 1) == "gemm"
+               and K.gemm_route(rows, N, Kd, 1) == "gemm"
+               for N, Kd in cls_tail_gemms(H, F))
+
+
+def cls_tail_same_kernel(B: int, rows: int, H: int, F: int) -> bool:
+    """Whether the CLS-only tail (M = B) runs each of its GEMMs on the
+    very kernel the full layer (M = rows) runs it on: same family and
+    same tile, hence the same order of additions per output element and
+    the same bits. Needs the extension for the tile half."""
+    return cls_tail_routes_match(B, rows, H, F) and all(
+        K.gemm_tile(B, N, Kd, 1) == K.gemm_tile(rows, N, Kd, 1)
+        for N, Kd in cls_tail_gemms(H, F))
+
+
 class BertEncoder:
     def __init__(self, cfg: BertConfig, weights: dict[str, torch.Tensor],
-                 use_fused_attn: bool = True):
+                 use_fused_attn: bool = True,
+                 fast_path: bool | frozenset[str] | set[str] = True):
         self.cfg = cfg
         self.w = weights
         # fused flash kernel supports d in {32,64,96,128}
         self.use_fused_attn = use_fused_attn and cfg.head_dim in (32, 64,
                                                                   96, 128)
+        # fast_path=False keeps the plain kernel sequence (the oracle of
+        # the fast path's tests); a set of FAST_ITEMS enables just those.
+        if isinstance(fast_path, bool):
+            fast_path = FAST_ITEMS if fast_path else frozenset()
+        self.fast = frozenset(fast_path)
+        assert self.fast <= FAST_ITEMS, f"unknown items {self.fast - FAST_ITEMS}"
+        if not self.use_fused_attn:
+            self.fast -= {"merge", "short", "tail"}
 
     # ------------------------------------------------------------- GPU
-    def forward(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
-        """ids [B,S] int32 (padded), lens [B] int32 -> [B,S,H] bf16."""
+    def forward(self, ids: torch.Tensor, lens: torch.Tensor,
+                cls_only: bool = False) -> torch.Tensor:
+        """ids [B,S] int32 (padded), lens [B] int32 -> [B,S,H] bf16, or
+        with cls_only the CLS rows alone, [B,1,H] (a strided view of the
+        full result where the last layer had to run in full)."""
         cfg, w = self.cfg, self.w
+        fast = self.fast
         B, S = ids.shape
         if S % 32 != 0:
             # PV GEMM contracts over S — pad to the MFMA K granularity;
@@ -94,42 +139,70 @@ class BertEncoder:
             ids = torch.nn.functional.pad(ids, (0, pad))
             S += pad
         H, nh, d = cfg.hidden, cfg.heads, cfg.head_dim
-        pos_ids = torch.arange(S, device=ids.device, dtype=torch.int32)\
-            .repeat(B)
-        x = K.gather(w["embed.word"], ids.reshape(-1))
-        x = K.add(x, K.gather(w["embed.pos"], pos_ids))
-        x = K.layernorm(x, w["embed.ln.g"], w["embed.ln.b"], eps=cfg.eps)
+        if "embed" in fast:
+            x = K.embed_layernorm(w["embed.word"], w["embed.pos"],
+                                  ids.reshape(-1), S, w["embed.ln.g"],
+                                  w["embed.ln.b"], eps=cfg.eps)
+        else:
+            pos_ids = torch.arange(S, device=ids.device, dtype=torch.int32)\
+                .repeat(B)
+            x = K.gather(w["embed.word"], ids.reshape(-1))
+            x = K.add(x, K.gather(w["embed.pos"], pos_ids))
+            x = K.layernorm(x, w["embed.ln.g"], w["embed.ln.b"], eps=cfg.eps)
 
-        # per-(batch*head) valid key lengths for the softmax mask
-        vl = lens.repeat_interleave(nh).contiguous()
         scale = d ** -0.5
         vl_b = lens.contiguous()
+        if not self.use_fused_attn:
+            # per-(batch*head) valid key lengths for the softmax mask
+            vl = lens.repeat_interleave(nh).contiguous()
+        variant = 0 if "short" in fast else 1
+        # CLS-only tail: after the last layer's K and V exist, only query
+        # row 0 of each sequence is needed — if its GEMMs stay on the
+        # kernels the full layer would run, so the bits stay the same.
+        tail = (cls_only and "tail" in fast
+                and cls_tail_same_kernel(B, B * S, H, cfg.ffn))
         for i in range(cfg.layers):
             p = f"layer.{i}."
             qkv = K.gemm_nt(x, w[p + "qkv.w"], bias=w[p + "qkv.b"])
+            Sq = 1 if tail and i == cfg.layers - 1 else S
             if self.use_fused_attn:
                 # zero-copy strided head views straight out of qkv
                 qkv5 = qkv.view(B, S, 3, nh, d)
-                qv = qkv5[:, :, 0].permute(0, 2, 1, 3)
+                qv = qkv5[:, :Sq, 0].permute(0, 2, 1, 3)
                 kv = qkv5[:, :, 1].permute(0, 2, 1, 3)
                 vv = qkv5[:, :, 2].permute(0, 2, 1, 3)
-                ctx = K.attn_fused(qv, kv, vv, valid_len=vl_b, scale=scale)
+                if "merge" in fast:
+                    # heads land in the merged layout: no merge_heads copy
+                    merged = torch.empty(B * Sq, H, device=x.device,
+                                         dtype=torch.bfloat16)
+                    K.attn_fused(qv, kv, vv, valid_len=vl_b, scale=scale,
+                                 out=merged.view(B, Sq, nh, d)
+                                 .permute(0, 2, 1, 3), variant=variant)
+                else:
+                    ctx = K.attn_fused(qv, kv, vv, valid_len=vl_b,
+                                       scale=scale, variant=variant)
+                    merged = K.merge_heads(ctx, B, Sq, nh, d)
             else:
                 q, k, vt = K.qkv_split(qkv, B, S, nh, nh, d)
                 scores = K.gemm_nt(q, k, out_f32=True, alpha=scale)
                 probs = K.softmax(scores, valid_len=vl)
                 ctx = K.gemm_nt(probs, vt)               # [G, S, d]
-            merged = K.merge_heads(ctx, B, S, nh, d)
+                merged = K.merge_heads(ctx, B, S, nh, d)
             attn = K.gemm_nt(merged, w[p + "attn_out.w"],
                              bias=w[p + "attn_out.b"])
+            # the tail's residual: the CLS rows of x, S*H elements apart
+            res = x.view(B, S, H)[:, 0] if Sq != S else x
             x = K.layernorm(attn, w[p + "ln1.g"], w[p + "ln1.b"],
-                            residual=x, eps=cfg.eps)
+                            residual=res, eps=cfg.eps)
             h = K.gemm_nt(x, w[p + "ffn_in.w"], bias=w[p + "ffn_in.b"],
                           act="gelu")
             o = K.gemm_nt(h, w[p + "ffn_out.w"], bias=w[p + "ffn_out.b"])
             x = K.layernorm(o, w[p + "ln2.g"], w[p + "ln2.b"],
                             residual=x, eps=cfg.eps)
-        return x.view(B, S, H)
+        if tail:
+            return x.view(B, 1, H)
+        x = x.view(B, S, H)
+        return x[:, :1] if cls_only else x
 
     # -------------------------------------------------- CPU fp32 oracle
     def forward_reference(self, ids: torch.Tensor,

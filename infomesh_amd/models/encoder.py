@@ -25,18 +25,22 @@ class EmbeddingEncoder:
 
     def __init__(self, device: str = "cuda", seed: int = 1234,
                  cfg: BertConfig = BGE_SMALL, max_len: int = 128,
-                 use_graph: bool = True):
+                 use_graph: bool = True,
+                 fast_path: bool | frozenset[str] | set[str] = True):
         self.cfg = cfg
         self.device = device
         self.max_len = max_len
         self.tokenizer = HashTokenizer(cfg.vocab_size)
-        self.bert = BertEncoder(cfg, init_bert_weights(cfg, seed, device))
+        # fast_path=False: the plain kernel sequence (bert.FAST_ITEMS)
+        self.bert = BertEncoder(cfg, init_bert_weights(cfg, seed, device),
+                                fast_path=fast_path)
         from ..ops.graphs import GraphedCallable
         self._graphed = GraphedCallable(self._encode_impl, enabled=use_graph)
 
     def _encode_impl(self, ids: torch.Tensor,
                      lens: torch.Tensor) -> torch.Tensor:
-        hidden = self.bert.forward(ids, lens)
+        # CLS pooling reads row 0 of each sequence only
+        hidden = self.bert.forward(ids, lens, cls_only=True)
         return K.pool(hidden, lens, mode="cls", l2=True)
 
     def encode_ids(self, ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:

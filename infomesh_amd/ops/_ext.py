@@ -24,7 +24,10 @@ _SIGNATURES: dict[str, list] = {
                               c_int, c_float, c_int, c_void_p],
     "infomesh_layernorm": [c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_long, c_int, c_float,
-                           c_void_p],
+                           c_long, c_void_p],
+    "infomesh_embed_layernorm": [c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_long, c_int, c_int,
+                                 c_float, c_void_p],
     "infomesh_rmsnorm": [c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p, c_long, c_int, c_float, c_void_p],
     "infomesh_softmax": [c_void_p, c_void_p, c_void_p, c_long, c_int,
@@ -76,7 +79,8 @@ _SIGNATURES: dict[str, list] = {
                             c_void_p, c_int, c_int, c_int, c_int, c_int,
                             c_int, c_long, c_long, c_long, c_long, c_long,
                             c_long, c_long, c_long, c_long,
-                            c_int, c_float, c_void_p],
+                            c_long, c_long, c_long,
+                            c_int, c_float, c_int, c_void_p],
     "infomesh_kv_append": [c_void_p, c_void_p, c_void_p, c_void_p,
                            c_void_p, c_int, c_int, c_int, c_int, c_void_p],
     "infomesh_dense_scores": [c_void_p, c_void_p, c_void_p,
@@ -140,6 +144,7 @@ _SIGNATURES: dict[str, list] = {
 # Everything not listed here returns void. topk_*_u32: lengths;
 # dense_scores, gemm_bf16_nt_bmax: dispatch eligibility (0 = launched);
 # gemm_tile: tile code; gemm_bmax_width: columns per block maximum;
+# attn_fused, embed_layernorm: 0 = launched, 1 = shape refused;
 # term_block_docs: documents per workgroup of term_bitmask; facet_*: the
 # chunk size and the slot layout of facet_counts; domtop_*: the chunk
 # size, the LDS table size and the K cap of csrc/domtop.hip; collapse_*:
@@ -164,7 +169,9 @@ _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
              "infomesh_gemm_bf16_nt_bmax": c_int,
              "infomesh_dense_scores": c_int,
              "infomesh_dense_scores_fp8": c_int,
-             "infomesh_gemm_tile": c_int}
+             "infomesh_gemm_tile": c_int,
+             "infomesh_attn_fused": c_int,
+             "infomesh_embed_layernorm": c_int}
 
 
 def _try_load() -> ctypes.CDLL | None:

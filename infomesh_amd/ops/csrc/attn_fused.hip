@@ -12,11 +12,20 @@
 //
 // Template D in {32, 64, 96, 128} covers bge-small (32), reranker (64),
 // phi-3 (96) and common 128-dim heads.
+//
+// The tile (QTILE query rows x KTILE keys, QTILE/16 waves) is a template
+// parameter of the one kernel body. The general tile is 64 x 64 with 4
+// waves; problems that fit whole into 32 x 32 (the encoder at S = 32,
+// its CLS-only tail at Sq = 1) run the short tile with 2 waves and skip
+// the two score chunks, the PV step and the staged keys that the general
+// tile spends on masked padding. The short tile gives the same bits:
+// masked keys add exact zeros to row_sum and to the PV accumulators,
+// chunks are added in ascending order, and a row's statistics do not
+// depend on other rows.
+//
+// The output is a strided view like the operands, so a caller can have
+// the heads written straight into the merged [B*S, nh*d] layout.
 #include "common.h"
-
-#define QTILE 64
-#define KTILE 64
-#define VPAD 72   // V^T LDS row stride (elems): 16-B-aligned rows + bank spread
 
 // Strided operands: element address = base + b*bs + h*hs + row*rs + j.
 // g = b*nhq + hq; kv head = hq / (nhq/nhk) — GQA without expansion.
@@ -24,18 +33,26 @@ struct TensorView {
   const bf16* ptr;
   long bs, hs, rs;
 };
+struct OutView {
+  bf16* ptr;
+  long bs, hs, rs;
+};
 
 namespace {
 
-template <int D>
-__global__ __launch_bounds__(256) void attn_fused_kernel(
+template <int D, int QTILE, int KTILE>
+__global__ __launch_bounds__(QTILE * 4) void attn_fused_kernel(
     TensorView Q, TensorView K, TensorView V,
     const int* __restrict__ valid_len,
-    bf16* __restrict__ O, int nhq, int nhk,
+    OutView O, int nhq, int nhk,
     int Sq, int Sk, int causal, float scale) {
+  constexpr int NW = QTILE / 16;            // waves, 16 q-rows each
+  constexpr int NT = NW * 64;               // threads per block
+  // V^T LDS row stride (elems): 16-B-aligned rows + bank spread
+  constexpr int VPAD = KTILE + 8;
   __shared__ bf16 k_lds[KTILE][D];          // [key][d] linear
   __shared__ bf16 vt_lds[D][VPAD];          // [d][key] transposed (+pad)
-  __shared__ bf16 p_lds[4][16][KTILE];      // per-wave P tiles
+  __shared__ bf16 p_lds[NW][16][KTILE];     // per-wave P tiles
   const int g = blockIdx.y;
   const int q0 = blockIdx.x * QTILE;
   const int lane = threadIdx.x & 63;
@@ -78,11 +95,11 @@ __global__ __launch_bounds__(256) void attn_fused_kernel(
   }
 
   for (int kv0 = 0; kv0 < kv_limit; kv0 += KTILE) {
-    // ---- cooperative staging (256 threads)
+    // ---- cooperative staging (all NT threads)
     {
-      // K: rows of 64 keys x D; thread -> (key, 8-elem d chunk)
+      // K: rows of KTILE keys x D; thread -> (key, 8-elem d chunk)
       const int perrow = D / 8;
-      for (int t = threadIdx.x; t < KTILE * perrow; t += 256) {
+      for (int t = threadIdx.x; t < KTILE * perrow; t += NT) {
         const int key = t / perrow, dc = (t % perrow) * 8;
         const int src = min(kv0 + key, Sk - 1);
         *reinterpret_cast<bf16x8*>(&k_lds[key][dc]) =
@@ -95,7 +112,7 @@ __global__ __launch_bounds__(256) void attn_fused_kernel(
     }
     __syncthreads();
 
-    // ---- S tile: 4 chunks of 16 keys
+    // ---- S tile: KTILE/16 chunks of 16 keys
     // mfma(A=qfrag, B=kfrag): C row=(lane>>4)*4+r = Q row,
     // col=lane&15 = key -> row stats reduce within 16-lane groups.
     f32x4 s_chunk[KTILE / 16];
@@ -198,7 +215,8 @@ __global__ __launch_bounds__(256) void attn_fused_kernel(
     __syncthreads();   // protect k_lds/vt_lds before next tile's staging
   }
 
-  // ---- epilogue: divide by l, store 16 rows x D
+  // ---- epilogue: divide by l, store 16 rows x D through the out view
+  bf16* Og = O.ptr + (long)b * O.bs + (long)hq * O.hs;
 #pragma unroll
   for (int f = 0; f < D / 16; ++f) {
 #pragma unroll
@@ -206,30 +224,23 @@ __global__ __launch_bounds__(256) void attn_fused_kernel(
       const int qrow = q0 + wid * 16 + crow0 + r;
       if (qrow >= Sq) continue;
       const float inv = l_run[r] > 0.f ? 1.0f / l_run[r] : 0.f;
-      O[(long)g * Sq * D + (long)qrow * D + f * 16 + ccol] =
-          f2bf(o_acc[f][r] * inv);
+      Og[(long)qrow * O.rs + f * 16 + ccol] = f2bf(o_acc[f][r] * inv);
     }
   }
 }
 
-}  // namespace
+constexpr int SHORT_TILE = 32;  // short variant: Sq and Sk both within it
 
-extern "C" void infomesh_attn_fused(
-    const void* Q, const void* K, const void* V, const void* valid_len,
-    void* O, int B, int nhq, int nhk, int Sq, int Sk, int D,
-    long qb, long qh, long qr, long kb, long kh, long kr,
-    long vb, long vh, long vr,
-    int causal, float scale, void* stream) {
-  auto s = reinterpret_cast<hipStream_t>(stream);
-  dim3 grid((Sq + QTILE - 1) / QTILE, B * nhq), block(256);
-  TensorView qv{(const bf16*)Q, qb, qh, qr};
-  TensorView kv{(const bf16*)K, kb, kh, kr};
-  TensorView vv{(const bf16*)V, vb, vh, vr};
+template <int QTILE, int KTILE>
+void launch_attn(int D, TensorView q, TensorView k, TensorView v,
+                 const int* valid_len, OutView o, int B, int nhq, int nhk,
+                 int Sq, int Sk, int causal, float scale, hipStream_t s) {
+  dim3 grid((Sq + QTILE - 1) / QTILE, B * nhq), block(QTILE * 4);
 #define CASE(DV)                                                          \
   case DV:                                                                \
-    hipLaunchKernelGGL(attn_fused_kernel<DV>, grid, block, 0, s,          \
-                       qv, kv, vv, (const int*)valid_len, (bf16*)O,       \
-                       nhq, nhk, Sq, Sk, causal, scale);                  \
+    hipLaunchKernelGGL((attn_fused_kernel<DV, QTILE, KTILE>), grid,       \
+                       block, 0, s, q, k, v, valid_len, o, nhq, nhk,      \
+                       Sq, Sk, causal, scale);                            \
     break;
   switch (D) {
     CASE(32) CASE(64) CASE(96) CASE(128)
@@ -237,4 +248,33 @@ extern "C" void infomesh_attn_fused(
       break;  // unsupported D: wrapper validates
   }
 #undef CASE
+}
+
+}  // namespace
+
+// variant: 0 = choose (the short tile whenever the problem fits it),
+// 1 = general 64 x 64 tile, 2 = short 32 x 32 tile. Returns 0, or 1
+// without launching when variant 2 is asked for a shape that does not
+// fit the short tile (or the variant is unknown).
+extern "C" int infomesh_attn_fused(
+    const void* Q, const void* K, const void* V, const void* valid_len,
+    void* O, int B, int nhq, int nhk, int Sq, int Sk, int D,
+    long qb, long qh, long qr, long kb, long kh, long kr,
+    long vb, long vh, long vr, long ob, long oh, long orow,
+    int causal, float scale, int variant, void* stream) {
+  auto s = reinterpret_cast<hipStream_t>(stream);
+  const bool fits = Sq <= SHORT_TILE && Sk <= SHORT_TILE;
+  if (variant < 0 || variant > 2 || (variant == 2 && !fits)) return 1;
+  TensorView qv{(const bf16*)Q, qb, qh, qr};
+  TensorView kv{(const bf16*)K, kb, kh, kr};
+  TensorView vv{(const bf16*)V, vb, vh, vr};
+  OutView ov{(bf16*)O, ob, oh, orow};
+  if (variant == 2 || (variant == 0 && fits))
+    launch_attn<SHORT_TILE, SHORT_TILE>(D, qv, kv, vv, (const int*)valid_len,
+                                        ov, B, nhq, nhk, Sq, Sk, causal,
+                                        scale, s);
+  else
+    launch_attn<64, 64>(D, qv, kv, vv, (const int*)valid_len, ov, B, nhq,
+                        nhk, Sq, Sk, causal, scale, s);
+  return 0;
 }

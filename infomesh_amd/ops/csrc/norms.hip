@@ -14,11 +14,11 @@ __global__ __launch_bounds__(256) void norm_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ res,
     bf16* __restrict__ out, bf16* __restrict__ res_out,
     const bf16* __restrict__ gamma, const bf16* __restrict__ beta,
-    int H, float eps) {
+    int H, float eps, long res_stride) {
   __shared__ float scratch[16];
   const long row = blockIdx.x;
   const bf16* xr = x + row * H;
-  const bf16* rr = RESIDUAL ? res + row * H : nullptr;
+  const bf16* rr = RESIDUAL ? res + row * res_stride : nullptr;
 
   // Pass 1: accumulate sums, keeping the (residual-added) values in regs
   // for rows up to 8*256*MAXV elements; fall back to re-read for huge H.
@@ -93,17 +93,25 @@ __global__ __launch_bounds__(256) void norm_kernel(
 // Wave-per-row variant for small H (<= 2048): 4 rows per 256-thread
 // block, reductions stay inside each wave (no LDS round trip). The
 // one-row-per-block kernel above idles (256 - H/8) threads at H=384.
-template <bool RMS, bool RESIDUAL>
+// The residual's rows are res_stride elements apart (H when packed; the
+// encoder's CLS-only tail reads every S-th row of the hidden state).
+// EMBED is the embedding front in one pass: x is the word table and res
+// the position table, row r normalizes bf16(x[ids[r]] + res[r % S]) —
+// the sum rounded to bf16 as the add kernel would have stored it.
+template <bool RMS, bool RESIDUAL, bool EMBED = false>
 __global__ __launch_bounds__(256) void norm_rowwave_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ res,
     bf16* __restrict__ out, bf16* __restrict__ res_out,
     const bf16* __restrict__ gamma, const bf16* __restrict__ beta,
-    long rows, int H, float eps) {
+    long rows, int H, float eps, long res_stride,
+    const int* __restrict__ ids, int S) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
-  const bf16* xr = x + row * H;
-  const bf16* rr = RESIDUAL ? res + row * H : nullptr;
+  const bf16* xr = x + (EMBED ? (long)ids[row] : row) * H;
+  const bf16* rr = EMBED      ? res + (row % S) * H
+                   : RESIDUAL ? res + row * res_stride
+                              : nullptr;
   const int nvec = H / 8;
   float f[8 * 4];  // up to H=2048: nvec<=256 -> <=4 vecs/lane
   float sum = 0.f, sumsq = 0.f;
@@ -112,7 +120,12 @@ __global__ __launch_bounds__(256) void norm_rowwave_kernel(
     bf16x8 xv = *reinterpret_cast<const bf16x8*>(xr + v * 8);
 #pragma unroll
     for (int j = 0; j < 8; ++j) f[it * 8 + j] = bf2f(xv[j]);
-    if (RESIDUAL) {
+    if (EMBED) {
+      bf16x8 rv = *reinterpret_cast<const bf16x8*>(rr + v * 8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        f[it * 8 + j] = bf2f(f2bf(f[it * 8 + j] + bf2f(rv[j])));
+    } else if (RESIDUAL) {
       bf16x8 rv = *reinterpret_cast<const bf16x8*>(rr + v * 8);
 #pragma unroll
       for (int j = 0; j < 8; ++j) f[it * 8 + j] += bf2f(rv[j]);
@@ -160,18 +173,20 @@ __global__ __launch_bounds__(256) void norm_rowwave_kernel(
     if (H <= 2048) {                                                      \
       dim3 g((unsigned)((rows + 3) / 4));                                 \
       hipLaunchKernelGGL((norm_rowwave_kernel<RMS, RES>), g, dim3(256),   \
-                         0, s, __VA_ARGS__, rows, H, eps);                \
+                         0, s, __VA_ARGS__, rows, H, eps, res_stride,     \
+                         nullptr, 1);                                     \
     } else {                                                              \
       dim3 g((unsigned)rows);                                             \
       hipLaunchKernelGGL((norm_kernel<RMS, RES>), g, dim3(256), 0, s,     \
-                         __VA_ARGS__, H, eps);                            \
+                         __VA_ARGS__, H, eps, res_stride);                \
     }                                                                     \
   } while (0)
 
+// res_stride: elements between the residual's rows (H when packed).
 extern "C" void infomesh_layernorm(
     const void* x, const void* residual, void* out, void* res_out,
     const void* gamma, const void* beta,
-    long rows, int H, float eps, void* stream) {
+    long rows, int H, float eps, long res_stride, void* stream) {
   auto s = reinterpret_cast<hipStream_t>(stream);
   if (residual)
     NORM_LAUNCH(false, true, (const bf16*)x, (const bf16*)residual,
@@ -186,10 +201,28 @@ extern "C" void infomesh_rmsnorm(
     const void* x, const void* residual, void* out, void* res_out,
     const void* gamma, long rows, int H, float eps, void* stream) {
   auto s = reinterpret_cast<hipStream_t>(stream);
+  const long res_stride = H;
   if (residual)
     NORM_LAUNCH(true, true, (const bf16*)x, (const bf16*)residual,
                 (bf16*)out, (bf16*)res_out, (const bf16*)gamma, nullptr);
   else
     NORM_LAUNCH(true, false, (const bf16*)x, nullptr, (bf16*)out,
                 nullptr, (const bf16*)gamma, nullptr);
+}
+
+// Embedding front in one kernel: out[r] = LN(bf16(word[ids[r]] +
+// pos[r % S])), the bits of gather, gather, add, layernorm. Returns 0,
+// or 1 without launching when H is outside the wave-per-row kernel.
+extern "C" int infomesh_embed_layernorm(
+    const void* word, const void* pos, const void* ids, void* out,
+    const void* gamma, const void* beta,
+    long rows, int S, int H, float eps, void* stream) {
+  auto s = reinterpret_cast<hipStream_t>(stream);
+  if (H > 2048 || H % 8 != 0 || S < 1) return 1;
+  dim3 g((unsigned)((rows + 3) / 4));
+  hipLaunchKernelGGL((norm_rowwave_kernel<false, false, true>), g, dim3(256),
+                     0, s, (const bf16*)word, (const bf16*)pos, (bf16*)out,
+                     nullptr, (const bf16*)gamma, (const bf16*)beta, rows, H,
+                     eps, (long)H, (const int*)ids, S);
+  return 0;
 }

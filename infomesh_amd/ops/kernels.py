@@ -179,21 +179,56 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
               residual: torch.Tensor | None = None, eps: float = 1e-12,
               return_residual: bool = False):
     """LayerNorm over the last dim; optionally fused residual add
-    (y = LN(x + residual)); returns (y, x+residual) if requested."""
+    (y = LN(x + residual)); returns (y, x+residual) if requested.
+    A 2-D residual may have any row stride that is a multiple of 8
+    (rows of a larger buffer); its elements must be contiguous."""
     H = x.shape[-1]
     assert H % 8 == 0
     rows = x.numel() // H
     _check(x, torch.bfloat16, "x")
     out = torch.empty_like(x)
     res_out = None
+    res_stride = H
     if residual is not None:
         assert residual.shape == x.shape
+        assert residual.dtype == torch.bfloat16 and residual.is_cuda
+        if not residual.is_contiguous():
+            assert residual.dim() == 2 and residual.stride(1) == 1 \
+                and residual.stride(0) >= H and residual.stride(0) % 8 == 0 \
+                and residual.storage_offset() % 8 == 0, \
+                "residual must be contiguous or a 2-D row-strided view"
+            res_stride = residual.stride(0)
         if return_residual:
             res_out = torch.empty_like(x)
     _ext.lib().infomesh_layernorm(
         x.data_ptr(), _ptr(residual), out.data_ptr(), _ptr(res_out),
-        gamma.data_ptr(), beta.data_ptr(), rows, H, eps, _ext.stream_ptr())
+        gamma.data_ptr(), beta.data_ptr(), rows, H, eps, res_stride,
+        _ext.stream_ptr())
     return (out, res_out) if return_residual else out
+
+
+def embed_layernorm(word: torch.Tensor, pos: torch.Tensor,
+                    ids: torch.Tensor, S: int, gamma: torch.Tensor,
+                    beta: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
+    """Embedding front in one kernel: out[r] = LN(bf16(word[ids[r]] +
+    pos[r % S])) for ids [rows] i32 — the bits of gather, gather, add,
+    layernorm. H <= 2048 (the wave-per-row norm kernel)."""
+    _check(word, torch.bfloat16, "word")
+    _check(pos, torch.bfloat16, "pos")
+    _check(ids, torch.int32, "ids")
+    _check(gamma, torch.bfloat16, "gamma")
+    _check(beta, torch.bfloat16, "beta")
+    H = word.shape[1]
+    assert pos.shape[1] == H and gamma.numel() == H and beta.numel() == H
+    assert 1 <= S <= pos.shape[0] and ids.numel() % S == 0
+    out = torch.empty((ids.numel(), H), device=word.device,
+                      dtype=torch.bfloat16)
+    rc = _ext.lib().infomesh_embed_layernorm(
+        word.data_ptr(), pos.data_ptr(), ids.data_ptr(), out.data_ptr(),
+        gamma.data_ptr(), beta.data_ptr(), ids.numel(), S, H, eps,
+        _ext.stream_ptr())
+    assert rc == 0, f"embed_layernorm does not cover H={H}"
+    return out
 
 
 def rmsnorm(x: torch.Tensor, gamma: torch.Tensor,
@@ -293,9 +328,16 @@ def gather(table: torch.Tensor, ids: torch.Tensor,
 
 def pool(x: torch.Tensor, lens: torch.Tensor | None = None,
          mode: str = "cls", l2: bool = True) -> torch.Tensor:
-    """[B,S,H] bf16 -> [B,H] f32 (CLS or masked-mean pooling, L2 option)."""
+    """[B,S,H] bf16 -> [B,H] f32 (CLS or masked-mean pooling, L2 option).
+    CLS pooling also takes the CLS rows alone as a strided [B,1,H] view
+    whose batch stride is a multiple of H."""
     B, S, H = x.shape
-    _check(x, torch.bfloat16, "x")
+    if mode == "cls" and S == 1 and not x.is_contiguous():
+        assert x.is_cuda and x.dtype == torch.bfloat16
+        assert x.stride(2) == 1 and x.stride(0) % H == 0 and x.stride(0) > 0
+        S = x.stride(0) // H      # the kernel reads row b*S of [B*S, H]
+    else:
+        _check(x, torch.bfloat16, "x")
     out = torch.empty((B, H), device=x.device, dtype=torch.float32)
     _ext.lib().infomesh_pool(
         x.data_ptr(), _ptr(lens), out.data_ptr(), B, S, H,
@@ -972,12 +1014,19 @@ def hamming_scan(queries: torch.Tensor, table: torch.Tensor,
 
 def attn_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                valid_len: torch.Tensor | None = None,
-               causal: bool = False, scale: float | None = None
-               ) -> torch.Tensor:
+               causal: bool = False, scale: float | None = None,
+               out: torch.Tensor | None = None, variant: int = 0
+               ) -> torch.Tensor | None:
     """Fused flash attention: q [B,nh,Sq,d], k/v [B,nhk,Sk,d] — any
     batch/head/row strides (element stride must be 1, d in {32,64,96,
     128}). GQA via nh % nhk == 0. valid_len: [B] i32 key limits.
-    Returns O [B*nh, Sq, d] bf16 contiguous."""
+    Returns O [B*nh, Sq, d] bf16 contiguous, or, given out= (a
+    [B,nh,Sq,d] bf16 view with element stride 1 and any other strides,
+    e.g. the head view of a merged [B*Sq, nh*d] buffer), writes there
+    and returns it. variant: 0 = the kernel's own choice, 1 = the
+    general 64x64 tile, 2 = the short 32x32 tile, which gives the same
+    bits and covers only Sq <= 32 and Sk <= 32: None, with nothing
+    launched, when asked for anything else."""
     assert q.dim() == 4 and k.dim() == 4 and v.dim() == 4
     B, nh, Sq, d = q.shape
     _, nhk, Sk, dk = k.shape
@@ -986,18 +1035,28 @@ def attn_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         assert t.dtype == torch.bfloat16 and t.stride(3) == 1
     if scale is None:
         scale = d ** -0.5
-    out = torch.empty(B * nh, Sq, d, device=q.device, dtype=torch.bfloat16)
+    assert k.shape[0] == B and v.shape == k.shape and Sq >= 1 and Sk >= 1
+    if out is None:
+        ret = torch.empty(B * nh, Sq, d, device=q.device,
+                          dtype=torch.bfloat16)
+        ostr = (nh * Sq * d, Sq * d, d)
+        optr = ret.data_ptr()
+    else:
+        assert out.shape == (B, nh, Sq, d) and out.is_cuda
+        assert out.dtype == torch.bfloat16 and out.stride(3) == 1
+        ret, ostr, optr = out, out.stride()[:3], out.data_ptr()
     if valid_len is not None:
         _check(valid_len, torch.int32, "valid_len")
         assert valid_len.numel() == B
-    _ext.lib().infomesh_attn_fused(
+    rc = _ext.lib().infomesh_attn_fused(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), _ptr(valid_len),
-        out.data_ptr(), B, nh, nhk, Sq, Sk, d,
+        optr, B, nh, nhk, Sq, Sk, d,
         q.stride(0), q.stride(1), q.stride(2),
         k.stride(0), k.stride(1), k.stride(2),
         v.stride(0), v.stride(1), v.stride(2),
-        int(causal), scale, _ext.stream_ptr())
-    return out
+        ostr[0], ostr[1], ostr[2],
+        int(causal), scale, variant, _ext.stream_ptr())
+    return ret if rc == 0 else None
 
 
 def attn_decode(q: torch.Tensor, k_cache: torch.Tensor,
