@@ -66,6 +66,14 @@ def per_domain_caps(per_domain, B: int) -> list[int] | None:
             f"per_domain: {caps}; 0 (no cap) or 1 <= m <= {COLLAPSE_M_MAX}")
     return caps if any(caps) else None
 
+
+def _mask_kw(mask) -> dict:
+    """A plane's mask, (bits, row_pred) or None, as the mask= / row_pred=
+    keywords of the ops.kernels calls."""
+    bits, row_pred = mask if mask is not None else (None, None)
+    return {"mask": bits, "row_pred": row_pred}
+
+
 # \w+ covers all unicode letters/digits (FTS5 unicode61 analogue);
 # diacritics are NFKD-folded below like unicode61 remove_diacritics
 _WORD_RE = re.compile(r"\w+")
@@ -822,10 +830,8 @@ class GpuShard:
                 rows_d = rows_t.to(self.device, non_blocking=True)
                 best = K.domain_best(
                     scores, rows_t, dom_id, D, m, plane == "bm25",
-                    mask=None if mask is None else mask[0],
-                    row_pred=None if mask is None else mask[1],
                     out=ws[:need].view(m, len(part), D),
-                    rows_device=rows_d)
+                    rows_device=rows_d, **_mask_kw(mask))
                 c_vals, c_idx = K.collapse_select(best, k)
                 at = rows_d.long()
                 vals.index_copy_(0, at, c_vals)
@@ -1061,8 +1067,7 @@ class GpuShard:
                 torch.from_numpy(t) for t in facets.tables())
             counts = K.facet_counts(
                 scores, rows_t, self.attrs, edges_t, langs_t, desc_t,
-                doms_t, mask=None if mask is None else mask[0],
-                row_pred=None if mask is None else mask[1])
+                doms_t, **_mask_kw(mask))
             tp = mark("shard.facets", tp)
         dom_top = tally = None
         if facets is not None and facets.top_rows:
@@ -1073,9 +1078,8 @@ class GpuShard:
             D = dom_keys.numel()
             cnt = K.domain_count(
                 scores, top_rows, dom_id, D,
-                mask=None if mask is None else mask[0],
-                row_pred=None if mask is None else mask[1],
-                out=self._domain_ws(len(facets.top_rows), D))
+                out=self._domain_ws(len(facets.top_rows), D),
+                **_mask_kw(mask))
             dom_top = K.domain_select(cnt, dom_keys, TOP_FETCH + 1)
             tally = DomainTally(cnt, dom_keys)
             tp = mark("shard.topdomains", tp)

@@ -6,8 +6,8 @@
 // list out.
 //
 // Sibling of domtop.hip: the same per-epoch tables (dom_id [N], a dense
-// id in [0, D) per document), the same grid, rows / bits / row_pred, and
-// for the BM25 form the same streaming read (match_queue.h).
+// id in [0, D) per document), the same grid and row prologue and, for the
+// BM25 form, the same streaming read (match_queue.h).
 //
 // Eligible. POSITIVE (BM25 plane): the match rule in the header of
 // facets.hip, mask bit and score > 0. Otherwise (dense plane): the mask
@@ -22,50 +22,33 @@
 // key 0 (that would take column 2^32 - 1): 0 marks an empty entry.
 //
 // domain_best. Workspace best [m, R, D] u64, zeroed by the caller.
-// Launched once per level j = 0 .. m-1, in stream order; grid
-// (R, ceil(N / COLLAPSE_CHUNK)). Every eligible document of the chunk
-// forms its key; at level j > 0 it takes part only if its key is strictly
-// below best[j-1][r, id] (a zero entry there: nothing is left in the
-// domain). The key is maxed into a per-workgroup LDS table keyed by id:
-// open addressing, COLLAPSE_SLOTS slots, linear probing, at most
-// COLLAPSE_PROBES probes; atomicCAS claims the slot, a 64-bit LDS
-// atomicMax holds the key. A key that finds no slot goes straight to a
-// global 64-bit atomicMax. After the chunk every occupied slot is flushed
-// with one global atomicMax. Max is exact in any order, so the result
-// depends on neither the table size nor the hash. After level j,
-// best[j][r, id] is the (j+1)-th largest key of domain id: the m tables
-// together are exactly the capped set.
+// Launched once per level j = 0 .. m-1, in stream order. Every eligible
+// document of the chunk forms its key; at level j > 0 it takes part only
+// if its key is strictly below best[j-1][r, id] (a zero entry there:
+// nothing is left in the domain). The key is maxed (64-bit LDS atomicMax)
+// under its id in the workgroup's LDS table (id_table.h), or straight
+// into best[j][r, id] when the table has no slot for it. After the chunk
+// every occupied slot is flushed with one global atomicMax. Max is exact
+// in any order. After level j, best[j][r, id] is the (j+1)-th largest key
+// of domain id: the m tables together are exactly the capped set.
 //
-// collapse_select. One workgroup per row; the k largest non-zero keys of
-// the row's m * D entries. A first read finds the largest key and the
-// number of non-zero entries; then an MSB-first radix select, 8 bits a
-// pass, straight from the tables, narrows down the bucket that holds the
-// k-th key. As soon as the keys above the bucket plus the bucket fit the
-// LDS candidate buffer they are gathered and sorted (bitonic), and the
-// first k are written as (score, column) decoded from the keys, -inf / -1
-// past the last one. Keys are distinct, so after all eight passes the
-// bucket holds one key and fewer than k lie above it: the loop always
-// ends with a set that fits. No host read-back, one launch.
+// collapse_select. One workgroup per row; key_select.h selects and sorts
+// the k largest non-zero keys of the row's m * D entries, straight from
+// the tables. The first k are written as (score, column) decoded from
+// the keys, -inf / -1 past the last one. No host read-back, one launch.
 #include "common.h"
+#include "id_table.h"
+#include "key_select.h"
 #include "match_queue.h"
 
 #define COLLAPSE_THREADS MATCHQ_THREADS
 #define COLLAPSE_CHUNK MATCHQ_CHUNK
 #define COLLAPSE_M_MAX 4
 #define COLLAPSE_K_MAX 1024
-#define COLLAPSE_SLOTS 2048     // LDS table of domain_best, a power of two
-#define COLLAPSE_SLOT_BITS 11
-#define COLLAPSE_PROBES 8
 #define COLSEL_THREADS 1024
 #define COLSEL_CAND 4096        // LDS candidate keys of collapse_select
-static_assert((1 << COLLAPSE_SLOT_BITS) == COLLAPSE_SLOTS, "power of two");
-static_assert(COLSEL_CAND >= COLLAPSE_K_MAX &&
-                  (COLSEL_CAND & (COLSEL_CAND - 1)) == 0,
-              "the candidates hold k keys and sort as a power of two");
 
 namespace {
-
-typedef unsigned long long u64;
 
 DEVINL u64 collapse_key(float score, long d) {
   return ((u64)float_to_ordered(score) << 32) |
@@ -78,26 +61,16 @@ __global__ __launch_bounds__(COLLAPSE_THREADS) void domain_best_kernel(
     const unsigned* __restrict__ bits, const int* __restrict__ row_pred,
     const int* __restrict__ dom_id, u64* __restrict__ best, long N, long W,
     int B, int P, int D, int R, int level) {
-  __shared__ int s_key[COLLAPSE_SLOTS];   // domain id, -1: free
-  __shared__ u64 s_best[COLLAPSE_SLOTS];
+  __shared__ int s_key[IDTAB_SLOTS];   // domain id, -1: free
+  __shared__ u64 s_best[IDTAB_SLOTS];
   __shared__ unsigned short s_q[POSITIVE ? COLLAPSE_CHUNK : 1];
   __shared__ unsigned s_n;
   const int tid = threadIdx.x;
   const int r = blockIdx.x;
-  // the caller checks rows and row_pred; the clamps keep a bad call
-  // inside the arrays all the same (block-uniform)
-  const int b = rows[r];
-  if (b < 0 || b >= B) return;
-  const unsigned* mrow = nullptr;
-  if constexpr (MASKED) {
-    const int p = row_pred[b];
-    if (p < 0 || p >= P) return;
-    mrow = bits + (long)p * W;
-  }
-  for (int i = tid; i < COLLAPSE_SLOTS; i += COLLAPSE_THREADS) {
-    s_key[i] = -1;
-    s_best[i] = 0;
-  }
+  int b;
+  const unsigned* mrow;
+  if (!match_row<MASKED>(rows, bits, row_pred, B, P, W, &b, &mrow)) return;
+  id_table_init<COLLAPSE_THREADS>(s_key, s_best);
   if (tid == 0) s_n = 0;
   __syncthreads();
 
@@ -115,17 +88,11 @@ __global__ __launch_bounds__(COLLAPSE_THREADS) void domain_best_kernel(
       const u64 p = prev[id];
       if (p == 0 || key >= p) return;
     }
-    unsigned slot =
-        ((unsigned)id * 2654435761u) >> (32 - COLLAPSE_SLOT_BITS);
-    for (int p = 0; p < COLLAPSE_PROBES; ++p) {
-      const int was = atomicCAS(&s_key[slot], -1, id);
-      if (was == -1 || was == id) {
-        atomicMax(&s_best[slot], key);
-        return;
-      }
-      slot = (slot + 1) & (COLLAPSE_SLOTS - 1);
-    }
-    atomicMax(&out[id], key);
+    const int slot = id_table_slot(s_key, id);
+    if (slot >= 0)
+      atomicMax(&s_best[slot], key);
+    else
+      atomicMax(&out[id], key);
   };
   if constexpr (POSITIVE) {
     match_queue_fill<MASKED>(row, mrow, c0, c1, N, s_q, &s_n);
@@ -146,7 +113,7 @@ __global__ __launch_bounds__(COLLAPSE_THREADS) void domain_best_kernel(
     }
   }
   __syncthreads();
-  for (int i = tid; i < COLLAPSE_SLOTS; i += COLLAPSE_THREADS) {
+  for (int i = tid; i < IDTAB_SLOTS; i += COLLAPSE_THREADS) {
     const int id = s_key[i];
     const u64 k = s_best[i];
     if (id >= 0 && k) atomicMax(&out[id], k);
@@ -170,126 +137,17 @@ DEVINL void for_entries(const u64* __restrict__ tabs, long stride, int m,
 __global__ __launch_bounds__(COLSEL_THREADS) void collapse_select_kernel(
     const u64* __restrict__ best, float* __restrict__ vals,
     int* __restrict__ idx, int R, int D, int m, int K) {
-  __shared__ u64 s_cand[COLSEL_CAND];
-  __shared__ unsigned s_hist[HIST8_U32];
-  __shared__ unsigned s_bins[256];
-  __shared__ u64 s_max;
-  __shared__ unsigned s_nnz, s_nc;
-  // the select's state, written by thread 0 between barriers
-  __shared__ u64 s_prefix, s_det;   // the bucket: key & det == prefix
-  __shared__ unsigned s_need, s_above, s_bucket;
+  __shared__ KeySelectLds<COLSEL_CAND> s_sel;
   const int tid = threadIdx.x;
   const int r = blockIdx.x;
   const u64* tabs = best + (long)r * D;
   const long stride = (long)R * D;
   K = min(max(K, 1), COLLAPSE_K_MAX);
-  if (tid == 0) {
-    s_max = 0;
-    s_nnz = 0;
-    s_nc = 0;
-  }
-  __syncthreads();
-  {
-    u64 mx = 0;
-    unsigned nz = 0;
-    for_entries(tabs, stride, m, D, [&](u64 k) {
-      mx = k > mx ? k : mx;
-      ++nz;
-    });
-    for (int off = 32; off > 0; off >>= 1) {
-      const u64 o = __shfl_xor(mx, off, WAVE);
-      mx = o > mx ? o : mx;
-      nz += __shfl_xor(nz, off, WAVE);
-    }
-    if ((tid & (WAVE - 1)) == 0 && nz) {
-      atomicMax(&s_max, mx);
-      atomicAdd(&s_nnz, nz);
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    s_prefix = 0;
-    s_det = 0;
-    s_need = (unsigned)K;
-    s_above = 0;
-    s_bucket = s_nnz;
-  }
-  __syncthreads();
-  // every key has no bit at or above `top`
-  int top = 0;
-  while (top < 64 && (s_max >> top)) ++top;
-  // all reads of the state below are behind a barrier and block-uniform
-  for (int shift = (top + 7) / 8 * 8 - 8;
-       shift >= 0 && s_above + s_bucket > COLSEL_CAND; shift -= 8) {
-    hist8_zero(s_hist);
-    __syncthreads();
-    const u64 prefix = s_prefix, det = s_det;
-    unsigned* mine = hist8_mine(s_hist);
-    for_entries(tabs, stride, m, D, [&](u64 k) {
-      if ((k & det) == prefix)
-        atomicAdd(&mine[(unsigned)(k >> shift) & 255u], 1u);
-    });
-    __syncthreads();
-    if (tid < 256) {
-      unsigned sum = 0;
-#pragma unroll
-      for (int c = 0; c < HIST8_COPIES; ++c)
-        sum += s_hist[c * HIST8_STRIDE + tid];
-      s_bins[tid] = sum;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      // the bin of the need-th largest key of the bucket, from the top
-      unsigned cum = 0;
-      int bin = 255;
-      for (; bin > 0; --bin) {
-        if (cum + s_bins[bin] >= s_need) break;
-        cum += s_bins[bin];
-      }
-      // the bucket holds at least `need` keys or all that are left: when
-      // the scan runs out at bin 0 that bin is the rest either way
-      s_above += cum;
-      s_need -= min(cum, s_need - 1);
-      s_bucket = s_bins[bin];
-      s_prefix = prefix | ((u64)bin << shift);
-      s_det = det | (255ull << shift);
-    }
-    __syncthreads();
-  }
-  // gather: every key whose determined bits are >= the prefix
-  {
-    const u64 prefix = s_prefix, det = s_det;
-    for_entries(tabs, stride, m, D, [&](u64 k) {
-      if ((k & det) >= prefix) {
-        const unsigned at = atomicAdd(&s_nc, 1u);
-        if (at < COLSEL_CAND) s_cand[at] = k;
-      }
-    });
-  }
-  __syncthreads();
-  const unsigned nc = min(s_nc, (unsigned)COLSEL_CAND);
-  unsigned n2 = 1;
-  while (n2 < nc) n2 <<= 1;
-  for (unsigned i = nc + tid; i < n2; i += COLSEL_THREADS) s_cand[i] = 0;
-  __syncthreads();
-  // bitonic sort, descending; every thread takes its pairs of a step
-  for (unsigned size = 2; size <= n2; size <<= 1) {
-    for (unsigned stride2 = size >> 1; stride2 > 0; stride2 >>= 1) {
-      for (unsigned t = (unsigned)tid; t < (n2 >> 1); t += COLSEL_THREADS) {
-        const unsigned lo = 2 * t - (t & (stride2 - 1));
-        const unsigned hi = lo + stride2;
-        const bool desc = (lo & size) == 0;
-        const u64 a = s_cand[lo], c = s_cand[hi];
-        if (desc ? a < c : a > c) {
-          s_cand[lo] = c;
-          s_cand[hi] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  const unsigned nc =
+      key_select_sorted<COLSEL_CAND, COLSEL_THREADS, COLLAPSE_K_MAX>(
+          s_sel, K, [=](auto f) { for_entries(tabs, stride, m, D, f); });
   for (int i = tid; i < K; i += COLSEL_THREADS) {
-    const u64 k = (unsigned)i < nc ? s_cand[i] : 0ull;
+    const u64 k = (unsigned)i < nc ? s_sel.cand[i] : 0ull;
     float v = -INFINITY;
     int at = -1;
     if (k) {
@@ -301,32 +159,12 @@ __global__ __launch_bounds__(COLSEL_THREADS) void collapse_select_kernel(
   }
 }
 
-template <bool POSITIVE>
-void launch_best(hipStream_t s, dim3 grid, const void* scores,
-                 const void* rows, const void* bits, const void* row_pred,
-                 const void* dom_id, void* best, long N, long W, int B,
-                 int P, int D, int R, int level) {
-  if (bits != nullptr && row_pred != nullptr) {
-    hipLaunchKernelGGL((domain_best_kernel<POSITIVE, true>), grid,
-                       dim3(COLLAPSE_THREADS), 0, s, (const float*)scores,
-                       (const int*)rows, (const unsigned*)bits,
-                       (const int*)row_pred, (const int*)dom_id, (u64*)best,
-                       N, W, B, P, D, R, level);
-  } else {
-    hipLaunchKernelGGL((domain_best_kernel<POSITIVE, false>), grid,
-                       dim3(COLLAPSE_THREADS), 0, s, (const float*)scores,
-                       (const int*)rows, (const unsigned*)nullptr,
-                       (const int*)nullptr, (const int*)dom_id, (u64*)best,
-                       N, W, B, P, D, R, level);
-  }
-}
-
 }  // namespace
 
 extern "C" int infomesh_collapse_m_max() { return COLLAPSE_M_MAX; }
 extern "C" int infomesh_collapse_k_max() { return COLLAPSE_K_MAX; }
 extern "C" int infomesh_collapse_chunk_docs() { return COLLAPSE_CHUNK; }
-extern "C" int infomesh_collapse_lds_slots() { return COLLAPSE_SLOTS; }
+extern "C" int infomesh_collapse_lds_slots() { return IDTAB_SLOTS; }
 
 // scores [B, N] f32, N < 2^31; rows [R] i32 in [0, B); bits [P, W] u32
 // with W * 32 >= N and row_pred [B] i32 in [0, P), or both null (no
@@ -343,12 +181,16 @@ extern "C" void infomesh_domain_best(
   const dim3 grid((unsigned)R,
                   (unsigned)((N + COLLAPSE_CHUNK - 1) / COLLAPSE_CHUNK));
   for (int level = 0; level < m; ++level) {
-    if (positive)
-      launch_best<true>(s, grid, scores, rows, bits, row_pred, dom_id, best,
-                        N, W, B, P, D, R, level);
-    else
-      launch_best<false>(s, grid, scores, rows, bits, row_pred, dom_id,
-                         best, N, W, B, P, D, R, level);
+    dispatch_bool(positive != 0, [&](auto pos) {
+      dispatch_masked(bits, row_pred, [&](auto masked) {
+        hipLaunchKernelGGL(
+            (domain_best_kernel<decltype(pos)::value,
+                                decltype(masked)::value>),
+            grid, dim3(COLLAPSE_THREADS), 0, s, (const float*)scores,
+            (const int*)rows, (const unsigned*)bits, (const int*)row_pred,
+            (const int*)dom_id, (u64*)best, N, W, B, P, D, R, level);
+      });
+    });
   }
 }
 

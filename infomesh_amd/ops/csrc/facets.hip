@@ -118,16 +118,11 @@ __global__ __launch_bounds__(FACET_THREADS) void facet_counts_kernel(
   __shared__ unsigned s_n;                     // how many are queued
   const int tid = threadIdx.x;
   const int r = blockIdx.x;
-  // the caller checks rows, the descriptors and the caps; the clamps keep
-  // a bad call inside the arrays all the same (everything block-uniform)
-  const int b = rows[r];
-  if (b < 0 || b >= B) return;
-  const unsigned* mrow = nullptr;
-  if constexpr (MASKED) {
-    const int p = row_pred[b];
-    if (p < 0 || p >= P) return;
-    mrow = bits + (long)p * W;
-  }
+  int b;
+  const unsigned* mrow;
+  if (!match_row<MASKED>(rows, bits, row_pred, B, P, W, &b, &mrow)) return;
+  // the caller checks the descriptors and the caps; the clamps keep a bad
+  // call inside the arrays all the same (everything block-uniform)
   E = min(max(E, 0), FACET_MAX_EDGES);
   L = min(max(L, 0), FACET_MAX_LANGS);
   const int lang_zero = facet_lang_zero(E), lang0 = facet_lang0(E);
@@ -219,21 +214,13 @@ extern "C" void infomesh_facet_counts(
   auto s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)R,
                   (unsigned)((N + FACET_CHUNK - 1) / FACET_CHUNK));
-  if (bits != nullptr && row_pred != nullptr) {
-    hipLaunchKernelGGL(facet_counts_kernel<true>, grid, dim3(FACET_THREADS),
-                       0, s, (const float*)scores, (const int*)rows,
-                       (const unsigned*)bits, (const int*)row_pred,
-                       (const uint4*)attrs, (const unsigned*)edges,
-                       (const unsigned*)langs, (const int2*)dom_desc,
-                       (const unsigned*)doms, (int*)counts, N, W, B, P, E, L,
-                       F, ndoms);
-  } else {
-    hipLaunchKernelGGL(facet_counts_kernel<false>, grid,
+  dispatch_masked(bits, row_pred, [&](auto masked) {
+    hipLaunchKernelGGL(facet_counts_kernel<decltype(masked)::value>, grid,
                        dim3(FACET_THREADS), 0, s, (const float*)scores,
-                       (const int*)rows, (const unsigned*)nullptr,
-                       (const int*)nullptr, (const uint4*)attrs,
+                       (const int*)rows, (const unsigned*)bits,
+                       (const int*)row_pred, (const uint4*)attrs,
                        (const unsigned*)edges, (const unsigned*)langs,
                        (const int2*)dom_desc, (const unsigned*)doms,
                        (int*)counts, N, W, B, P, E, L, F, ndoms);
-  }
+  });
 }

@@ -1,10 +1,14 @@
-// The streaming read shared by facets.hip and domtop.hip: queue, in LDS,
-// the chunk-local numbers of a chunk's matching documents.
+// What the kernels over a query row's whole match set share (facets.hip,
+// domtop.hip, collapse.hip): the grid (R, ceil(N / MATCHQ_CHUNK)), the
+// row prologue and its mask dispatch, and the streaming read that
+// queues, in LDS, the chunk-local numbers of a chunk's matching
+// documents.
 //
 // The match rule is the one in the header of facets.hip: document d
 // matches iff it passes the row's mask (bit d of mrow; every document
 // passes when there is no mask) and row[d] > 0.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 #define MATCHQ_THREADS 256
@@ -12,6 +16,44 @@
 static_assert(MATCHQ_CHUNK <= 65536 &&
                   MATCHQ_CHUNK % (MATCHQ_THREADS * 4) == 0,
               "the queue holds chunk-local u16 document numbers");
+
+// The row prologue: workgroup row r = blockIdx.x works on batch row
+// *b = rows[r], under mask row *mrow = bits + row_pred[*b] * W (null
+// when not MASKED). The caller checks rows and row_pred on the host; the
+// clamps keep a bad call inside the arrays all the same: false (block-
+// uniform) means the workgroup has nothing to do and returns.
+template <bool MASKED>
+DEVINL bool match_row(const int* __restrict__ rows,
+                      const unsigned* __restrict__ bits,
+                      const int* __restrict__ row_pred, int B, int P, long W,
+                      int* b, const unsigned** mrow) {
+  *mrow = nullptr;
+  *b = rows[(int)blockIdx.x];
+  if (*b < 0 || *b >= B) return false;
+  if constexpr (MASKED) {
+    const int p = row_pred[*b];
+    if (p < 0 || p >= P) return false;
+    *mrow = bits + (long)p * W;
+  }
+  return true;
+}
+
+// Host side: f(std::true_type{}) or f(std::false_type{}) as `on` says, so
+// a launcher writes its launch once, with decltype(arg)::value as the
+// kernel's template argument.
+template <typename F>
+inline void dispatch_bool(bool on, F f) {
+  if (on)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+// The call has a mask when bits and row_pred are both given; the
+// unmasked kernels read neither pointer.
+template <typename F>
+inline void dispatch_masked(const void* bits, const void* row_pred, F f) {
+  dispatch_bool(bits != nullptr && row_pred != nullptr, f);
+}
 
 // Walks documents [c0, c1) of `row` (c1 <= N, c1 - c0 <= MATCHQ_CHUNK, c0
 // a multiple of MATCHQ_CHUNK) four per lane: one 32-bit mask word covers

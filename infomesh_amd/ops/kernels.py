@@ -636,6 +636,48 @@ def _host_words(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.cpu()
 
 
+def _match_rows(scores: torch.Tensor, rows: torch.Tensor,
+                mask: torch.Tensor | None, row_pred: torch.Tensor | None,
+                chunk_docs: int) -> tuple[int, int, int, int, int]:
+    """The shared front of facet_counts, domain_count and domain_best:
+    scores [B, N] f32 and, with a mask, mask [P, W] i32 + row_pred [B]
+    i32, on the device; rows [R] i32 read on the host (a device tensor
+    is copied back) and checked against B before a kernel indexes with
+    it; at most 65535 chunks of chunk_docs documents, the grid's y
+    limit. Returns (B, N, P, W, R); P = W = 0 without a mask."""
+    _check(scores, torch.float32, "scores")
+    assert scores.dim() == 2
+    B, N = scores.shape
+    assert N >= 1
+    assert (mask is None) == (row_pred is None), \
+        "mask and row_pred go together"
+    W = P = 0
+    if mask is not None:
+        _check(mask, torch.int32, "mask")
+        _check(row_pred, torch.int32, "row_pred")
+        assert mask.dim() == 2 and mask.shape[1] * 32 >= N
+        assert row_pred.numel() == B
+        P, W = mask.shape
+    h_rows = _host_words(rows, "rows")
+    assert h_rows.dim() == 1 and h_rows.numel() >= 1, "rows: [R], R >= 1"
+    assert bool(((h_rows >= 0) & (h_rows < B)).all()), \
+        "rows points outside the batch"
+    assert (N + chunk_docs - 1) // chunk_docs <= 65535
+    return B, N, P, W, h_rows.numel()
+
+
+def _zeroed(out: torch.Tensor | None, shape: tuple[int, ...],
+            dtype: torch.dtype, device: torch.device) -> torch.Tensor:
+    """The kernels' zeroed result: a fresh tensor, or the caller's
+    contiguous device workspace `out` of that shape and dtype, zeroed."""
+    if out is None:
+        return torch.zeros(shape, device=device, dtype=dtype)
+    _check(out, dtype, "out")
+    assert out.shape == shape, f"out: {list(shape)}"
+    out.zero_()
+    return out
+
+
 def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
                  attrs: torch.Tensor, edges: torch.Tensor,
                  langs: torch.Tensor, dom_desc: torch.Tensor,
@@ -656,29 +698,17 @@ def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
     (they are then uploaded, no sync) or as device tensors (copied back
     to check). More than 7 edges, 32 languages or 64 hashes in one list
     is a ValueError, and nothing is launched."""
-    _check(scores, torch.float32, "scores")
     _check(attrs, torch.int32, "attrs")
-    assert scores.dim() == 2
-    B, N = scores.shape
-    assert N >= 1 and attrs.shape == (N, 4), "attrs: [N, 4]"
-    assert (mask is None) == (row_pred is None), \
-        "mask and row_pred go together"
-    W = P = 0
-    if mask is not None:
-        _check(mask, torch.int32, "mask")
-        _check(row_pred, torch.int32, "row_pred")
-        assert mask.dim() == 2 and mask.shape[1] * 32 >= N
-        assert row_pred.numel() == B
-        P, W = mask.shape
-    h_rows = _host_words(rows, "rows")
+    B, N, P, W, R = _match_rows(scores, rows, mask, row_pred,
+                                facet_chunk_docs())
+    assert attrs.shape == (N, 4), "attrs: [N, 4]"
     h_edges = _host_words(edges, "edges")
     h_langs = _host_words(langs, "langs")
     h_desc = _host_words(dom_desc, "dom_desc")
     h_doms = _host_words(doms, "doms")
-    assert h_rows.dim() == 1 and h_edges.dim() == 1 and h_langs.dim() == 1 \
-        and h_doms.dim() == 1
-    R, E, L = h_rows.numel(), h_edges.numel(), h_langs.numel()
-    assert 1 <= R and h_desc.shape == (R, 2), "dom_desc: [R, 2]"
+    assert h_edges.dim() == 1 and h_langs.dim() == 1 and h_doms.dim() == 1
+    E, L = h_edges.numel(), h_langs.numel()
+    assert h_desc.shape == (R, 2), "dom_desc: [R, 2]"
     off, n = h_desc[:, 0].long(), h_desc[:, 1].long()
     assert bool((n >= 0).all()) and bool((off >= 0).all()) \
         and bool((off + n <= h_doms.numel()).all()), \
@@ -689,8 +719,6 @@ def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
             f"facets: {E} date edges, {L} languages, {Dw} domains in one "
             f"list; the caps are {FACET_MAX_EDGES}, {FACET_MAX_LANGS} and "
             f"{FACET_MAX_DOMS}")
-    assert bool((h_rows >= 0).all()) and bool((h_rows < B).all()), \
-        "rows points outside the batch"
 
     def asc(t, strict):
         u = t.long() & 0xFFFFFFFF
@@ -701,7 +729,6 @@ def facet_counts(scores: torch.Tensor, rows: torch.Tensor,
     assert all(asc(h_doms[o:o + c], True)
                for o, c in zip(off.tolist(), n.tolist())), \
         "doms: every list ascending as unsigned and unique"
-    assert (N + facet_chunk_docs() - 1) // facet_chunk_docs() <= 65535
     dev = scores.device
     tables = (dom_desc, rows, edges, langs, doms)
     if not any(t.is_cuda for t in tables):
@@ -754,36 +781,15 @@ def domain_count(scores: torch.Tensor, rows: torch.Tensor,
     contiguous [R, D] i32 device tensor to count into; it is zeroed
     here. Returns cnt [R, D] i32. dom_id is the caller's to keep inside
     [0, D): the kernel drops an id outside it."""
-    _check(scores, torch.float32, "scores")
     _check(dom_id, torch.int32, "dom_id")
-    assert scores.dim() == 2
-    B, N = scores.shape
     if D < 1:
         raise ValueError(f"domain_count: D = {D}; at least one domain")
-    assert N >= 1 and dom_id.shape == (N,), "dom_id: [N]"
-    assert (mask is None) == (row_pred is None), \
-        "mask and row_pred go together"
-    W = P = 0
-    if mask is not None:
-        _check(mask, torch.int32, "mask")
-        _check(row_pred, torch.int32, "row_pred")
-        assert mask.dim() == 2 and mask.shape[1] * 32 >= N
-        assert row_pred.numel() == B
-        P, W = mask.shape
-    h_rows = _host_words(rows, "rows")
-    assert h_rows.dim() == 1 and h_rows.numel() >= 1, "rows: [R], R >= 1"
-    R = h_rows.numel()
-    assert bool(((h_rows >= 0) & (h_rows < B)).all()), \
-        "rows points outside the batch"
-    assert (N + domtop_chunk_docs() - 1) // domtop_chunk_docs() <= 65535
+    B, N, P, W, R = _match_rows(scores, rows, mask, row_pred,
+                                domtop_chunk_docs())
+    assert dom_id.shape == (N,), "dom_id: [N]"
     dev = scores.device
     rows_d = rows if rows.is_cuda else rows.to(dev, non_blocking=True)
-    if out is None:
-        out = torch.zeros((R, D), device=dev, dtype=torch.int32)
-    else:
-        _check(out, torch.int32, "out")
-        assert out.shape == (R, D), "out: [R, D]"
-        out.zero_()
+    out = _zeroed(out, (R, D), torch.int32, dev)
     _ext.lib().infomesh_domain_count(
         scores.data_ptr(), rows_d.data_ptr(), _ptr(mask), _ptr(row_pred),
         dom_id.data_ptr(), out.data_ptr(), B, R, N, W, P, D,
@@ -856,32 +862,18 @@ def domain_best(scores: torch.Tensor, rows: torch.Tensor,
     bits: best[j, r, i] is the (j+1)-th largest key of domain i in row
     rows[r], 0 when the domain has no such document. m outside
     1 .. collapse_m_max() is a ValueError, and nothing is launched."""
-    _check(scores, torch.float32, "scores")
     _check(dom_id, torch.int32, "dom_id")
-    assert scores.dim() == 2
-    B, N = scores.shape
     if not 1 <= m <= collapse_m_max():
         raise ValueError(
             f"domain_best: m = {m}; 1 <= m <= {collapse_m_max()}")
     if D < 1:
         raise ValueError(f"domain_best: D = {D}; at least one domain")
-    assert 1 <= N < 2 ** 31 and dom_id.shape == (N,), "dom_id: [N]"
-    assert (mask is None) == (row_pred is None), \
-        "mask and row_pred go together"
-    W = P = 0
-    if mask is not None:
-        _check(mask, torch.int32, "mask")
-        _check(row_pred, torch.int32, "row_pred")
-        assert mask.dim() == 2 and mask.shape[1] * 32 >= N
-        assert row_pred.numel() == B
-        P, W = mask.shape
-    h_rows = _host_words(rows, "rows")
-    assert h_rows.dim() == 1 and h_rows.numel() >= 1, "rows: [R], R >= 1"
-    R = h_rows.numel()
-    assert bool(((h_rows >= 0) & (h_rows < B)).all()), \
-        "rows points outside the batch"
+    N = scores.shape[-1]
     if (N + collapse_chunk_docs() - 1) // collapse_chunk_docs() > 65535:
         raise ValueError(f"domain_best: N = {N}; more than 65535 chunks")
+    B, N, P, W, R = _match_rows(scores, rows, mask, row_pred,
+                                collapse_chunk_docs())
+    assert N < 2 ** 31 and dom_id.shape == (N,), "dom_id: [N]"
     dev = scores.device
     if rows_device is not None:
         assert not rows.is_cuda and rows_device.is_cuda \
@@ -890,12 +882,7 @@ def domain_best(scores: torch.Tensor, rows: torch.Tensor,
         rows_d = rows_device
     else:
         rows_d = rows if rows.is_cuda else rows.to(dev, non_blocking=True)
-    if out is None:
-        out = torch.zeros((m, R, D), device=dev, dtype=torch.int64)
-    else:
-        _check(out, torch.int64, "out")
-        assert out.shape == (m, R, D), "out: [m, R, D]"
-        out.zero_()
+    out = _zeroed(out, (m, R, D), torch.int64, dev)
     _ext.lib().infomesh_domain_best(
         scores.data_ptr(), rows_d.data_ptr(), _ptr(mask), _ptr(row_pred),
         dom_id.data_ptr(), out.data_ptr(), B, R, N, W, P, D, m,

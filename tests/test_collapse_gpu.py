@@ -16,6 +16,7 @@ if torch.cuda.is_available():
 import term_ops_corpus as C
 from infomesh_amd.ops import kernels as K
 from infomesh_amd.ops import reference as R
+from match_set_cases import B, GARBAGE, SCORES, _mask, _size
 
 
 @pytest.fixture(autouse=True)
@@ -25,35 +26,9 @@ def _gpu():
     torch.manual_seed(0)
 
 
-B = 4
-GARBAGE = 3.0e38        # the skipped row: every document would be first
-SCORES = np.asarray([0.0, -0.0, -1.0, 1.5e-30, 0.75, 2.0e30],
-                    dtype=np.float32)
 EDGES = np.asarray([0.0, -0.0, np.inf, -np.inf, -1.0, 1.0, -3.0e38],
                    dtype=np.float32)
 SIZES = ["1", "63", "64", "65", "257", "C-1", "C", "C+1", "2C+37"]
-
-
-def _size(name: str, CH: int) -> int:
-    return {"1": 1, "63": 63, "64": 64, "65": 65, "257": 257, "C-1": CH - 1,
-            "C": CH, "C+1": CH + 1, "2C+37": 2 * CH + 37}[name]
-
-
-def _mask(N: int, CH: int, rng) -> torch.Tensor:
-    """The mask rows of tests/test_top_domains_gpu.py: random bits with
-    zero words at every chunk's first and last 128-byte score line; all
-    zero; all ones."""
-    W = (N + 63) // 64 * 2
-    ok = np.zeros((3, W * 32), dtype=bool)
-    ok[0, :N] = rng.random(N) < 0.6
-    ok[2, :N] = True
-    words = np.packbits(ok, axis=1, bitorder="little").view(np.uint32) \
-        .reshape(3, W).copy()
-    if N > 64:
-        for c0 in range(0, N, CH):
-            words[0, c0 // 32] = 0
-            words[0, (min(c0 + CH, N) - 1) // 32] = 0
-    return torch.from_numpy(words.view(np.int32))
 
 
 def _scores(form: str, N: int, rng) -> np.ndarray:
@@ -184,6 +159,94 @@ def test_a_domain_with_fewer_than_m_eligible_documents():
     vals, idx = _collapse(scores, [0], dom, 3, 1, [8], True)
     assert idx[0].tolist() == [21, 20, 9, -1, -1, -1, -1, -1]
     assert vals[0, :3].tolist() == [3.0, 2.0, 1.0]
+
+
+# ------------------------------------- collapse_select on hand-built keys
+
+SELECT_KS = (1, 1024)
+
+
+def _hand_keys(scores: np.ndarray, cols: np.ndarray) -> np.ndarray:
+    """collapse.hip's key, float_to_ordered(score) << 32 |
+    (0xFFFFFFFF - col), in numpy."""
+    u = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32)
+    okey = np.where(u >> 31 != 0, ~u, u | np.uint32(0x80000000))
+    return (okey.astype(np.uint64) << np.uint64(32)) \
+        | (0xFFFFFFFF - cols).astype(np.uint64)
+
+
+def _decode_keys(keys: np.ndarray, k: int):
+    """The first k of `keys` (sorted) as (vals, idx), -inf / -1 behind."""
+    hi = (keys[:k] >> np.uint64(32)).astype(np.uint32)
+    bits = np.where(hi >> 31 != 0, hi & np.uint32(0x7FFFFFFF), ~hi)
+    vals = np.full(k, -np.inf, dtype=np.float32)
+    idx = np.full(k, -1, dtype=np.int32)
+    vals[:len(hi)] = bits.astype(np.uint32).view(np.float32)
+    idx[:len(hi)] = (0xFFFFFFFF - (keys[:k] & np.uint64(0xFFFFFFFF))) \
+        .astype(np.int64)
+    return vals, idx
+
+
+def _select_case(nnz: int, m: int):
+    """best [m, 2, D] u64 holding nnz keys per row among zeros, and per k
+    of SELECT_KS the oracle (vals [2, k], idx [2, k]): np.sort of the
+    row's non-zero keys, descending, decoded. Row 0: scores from EDGES
+    and normals, columns below 2^31. Row 1: one score and columns below
+    2^24, so all keys share their top 40 bits."""
+    rng = np.random.default_rng(nnz * 5 + m)
+    D = (nnz + m - 1) // m + 37
+    s0 = rng.standard_normal(nnz).astype(np.float32)
+    edge = rng.random(nnz) < 0.5
+    s0[edge] = rng.choice(EDGES, size=int(edge.sum()))
+    c0 = rng.choice(1 << 20, size=nnz, replace=False).astype(np.int64) \
+        * 2047 + rng.integers(0, 2047, size=nnz)
+    c1 = rng.choice(1 << 24, size=nnz, replace=False).astype(np.int64)
+    rows = [_hand_keys(s0, c0),
+            _hand_keys(np.full(nnz, 0.75, dtype=np.float32), c1)]
+    assert ((rows[1] >> np.uint64(24)) == (rows[1][:1] >> np.uint64(24))).all()
+    best = np.zeros((m, 2, D), dtype=np.uint64)
+    want = {k: ([], []) for k in SELECT_KS}
+    for r, keys in enumerate(rows):
+        assert len(np.unique(keys)) == nnz and (keys != 0).all()
+        at = rng.choice(m * D, size=nnz, replace=False)
+        best[at // D, r, at % D] = keys
+        tab = best[:, r, :].reshape(-1)
+        ordered = np.sort(tab[tab != 0])[::-1]
+        assert len(ordered) == nnz
+        for k in SELECT_KS:
+            vals, idx = _decode_keys(ordered, k)
+            # the oracle's own invariants: real entries first, in key
+            # order, every one a pair that went in
+            n = min(nnz, k)
+            assert (idx[:n] >= 0).all() and (idx[n:] == -1).all()
+            assert (vals[n:] == -np.inf).all()
+            assert (_hand_keys(vals[:n], idx[:n].astype(np.int64))
+                    == ordered[:n]).all()
+            assert (ordered[:-1] > ordered[1:]).all()
+            want[k][0].append(vals)
+            want[k][1].append(idx)
+    return best, {k: (np.stack(v), np.stack(i)) for k, (v, i) in want.items()}
+
+
+@pytest.mark.parametrize("m", [1, 4])
+@pytest.mark.parametrize("nnz", [0, 1, 1023, 1024, 1025, 2049, 4096, 4097,
+                                 20000])
+def test_collapse_select_on_hand_built_keys(nnz, m):
+    """collapse_select alone, on keys built here: the non-zero counts
+    around k = 1024, around the 4096 candidate keys it sorts in LDS
+    (2049 pads to 4096; 4096 fills it with no radix pass; 4097 forces
+    one) and far above; row 1 takes several passes to tell its keys
+    apart."""
+    best, want = _select_case(nnz, m)
+    best_t = torch.from_numpy(best.view(np.int64)).cuda()
+    for k in SELECT_KS:
+        vals, idx = K.collapse_select(best_t, k)
+        torch.cuda.synchronize()
+        assert vals.shape == idx.shape == (2, k)
+        assert np.array_equal(idx.cpu().numpy(), want[k][1]), (nnz, m, k)
+        # bit for bit: -0.0 is not +0.0 here
+        assert np.array_equal(vals.cpu().numpy().view(np.int32),
+                              want[k][0].view(np.int32)), (nnz, m, k)
 
 
 def test_over_a_cap_is_a_value_error_before_the_launch():

@@ -20,6 +20,7 @@ from infomesh_amd.index.doc_attrs import (FacetSpec, facet_results, lang16,
                                           pack_facets)
 from infomesh_amd.ops import kernels as K
 from infomesh_amd.ops import reference as R
+from match_set_cases import B, GARBAGE, SCORES, _mask, _size, _u
 
 
 @pytest.fixture(autouse=True)
@@ -31,10 +32,6 @@ def _gpu():
 
 # ------------------------------------------------- kernel vs the oracle
 
-B = 4
-GARBAGE = 3.0e38        # the skipped row: every document would match
-SCORES = np.asarray([0.0, -0.0, -1.0, 1.5e-30, 0.75, 2.0e30],
-                    dtype=np.float32)
 LANGS = sorted(lang16(c) for c in ("de", "en", "ja"))
 EDGES = [1000, 2000, 0x80000000]
 W0_POOL = [0, 1, 999, 1000, 1001, 2000, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF]
@@ -45,40 +42,12 @@ HASHES = sorted([7, 0x1234, 0x7FFFFFFF, 0x80000000, 0x80000001, 0xDEADBEEF,
 NOWHERE = 0x55555555                          # a hash in no document
 
 
-def _u(values) -> torch.Tensor:
-    return torch.from_numpy(np.asarray(values, dtype=np.uint32)
-                            .reshape(-1).view(np.int32))
-
-
-def _size(name: str, CH: int) -> int:
-    return {"1": 1, "63": 63, "64": 64, "65": 65, "255": 255, "256": 256,
-            "257": 257, "C-1": CH - 1, "C": CH, "C+1": CH + 1,
-            "2C+37": 2 * CH + 37}[name]
-
-
 def _attrs(N: int, rng) -> np.ndarray:
     a = np.zeros((N, 4), dtype=np.uint32)
     a[:, 0] = rng.choice(np.asarray(W0_POOL, dtype=np.uint32), size=N)
     a[:, 1] = rng.choice(np.asarray(W1_POOL, dtype=np.uint32), size=N)
     a[:, 2] = rng.choice(np.asarray(HASHES, dtype=np.uint32), size=N)
     return a
-
-
-def _mask(N: int, CH: int, rng) -> torch.Tensor:
-    """Three mask rows: random bits with zero words at every chunk's
-    first and last 128-byte score line; all zero; all ones (nobody's)."""
-    W = (N + 63) // 64 * 2
-    ok = np.zeros((3, W * 32), dtype=bool)
-    ok[0, :N] = rng.random(N) < 0.6
-    ok[2, :N] = True
-    words = np.packbits(ok, axis=1, bitorder="little").view(np.uint32) \
-        .reshape(3, W).copy()
-    if N > 64:                # (at N <= 64 that would leave nothing)
-        for c0 in range(0, N, CH):
-            words[0, c0 // 32] = 0
-            last = (min(c0 + CH, N) - 1) // 32
-            words[0, last] = 0
-    return torch.from_numpy(words.view(np.int32))
 
 
 def _invariants(counts: np.ndarray, E: int, L: int) -> None:

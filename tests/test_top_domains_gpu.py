@@ -19,6 +19,7 @@ from infomesh_amd.index.doc_attrs import (TOP_FETCH, FacetSpec, domain_hash,
                                           domain_tables_np, pack_facets)
 from infomesh_amd.ops import kernels as K
 from infomesh_amd.ops import reference as R
+from match_set_cases import B, GARBAGE, SCORES, _mask, _size, _u
 
 
 @pytest.fixture(autouse=True)
@@ -26,39 +27,6 @@ def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     torch.manual_seed(0)
-
-
-B = 4
-GARBAGE = 3.0e38        # the skipped row: every document would match
-SCORES = np.asarray([0.0, -0.0, -1.0, 1.5e-30, 0.75, 2.0e30],
-                    dtype=np.float32)
-
-
-def _u(values) -> torch.Tensor:
-    return torch.from_numpy(np.asarray(values, dtype=np.uint32)
-                            .reshape(-1).view(np.int32))
-
-
-def _size(name: str, CH: int) -> int:
-    return {"1": 1, "63": 63, "64": 64, "65": 65, "257": 257, "C-1": CH - 1,
-            "C": CH, "C+1": CH + 1, "2C+37": 2 * CH + 37}[name]
-
-
-def _mask(N: int, CH: int, rng) -> torch.Tensor:
-    """The mask rows of tests/test_facets_gpu.py: random bits with zero
-    words at every chunk's first and last 128-byte score line; all zero;
-    all ones."""
-    W = (N + 63) // 64 * 2
-    ok = np.zeros((3, W * 32), dtype=bool)
-    ok[0, :N] = rng.random(N) < 0.6
-    ok[2, :N] = True
-    words = np.packbits(ok, axis=1, bitorder="little").view(np.uint32) \
-        .reshape(3, W).copy()
-    if N > 64:
-        for c0 in range(0, N, CH):
-            words[0, c0 // 32] = 0
-            words[0, (min(c0 + CH, N) - 1) // 32] = 0
-    return torch.from_numpy(words.view(np.int32))
 
 
 def _count(scores, rows, dom_id, D, mask=None, row_pred=None, out=None):
@@ -193,6 +161,29 @@ def test_domain_select_exact(K_):
         # real entries come first, counts descend
         assert (real[:, :-1] >= real[:, 1:]).all()
         assert (want[:, :-1, 1] >= want[:, 1:, 1]).all()
+
+
+def _boundary_rows(D: int, rng) -> np.ndarray:
+    """Every count non-zero, so the select sees exactly D keys."""
+    return np.stack([np.full(D, 5),                        # all equal
+                     np.arange(1, D + 1),                  # all distinct
+                     rng.integers(1, 3, size=D)])          # two values
+
+
+@pytest.mark.parametrize("K_", [1, 65])
+@pytest.mark.parametrize("D", [2047, 2048, 2049, 4097])
+def test_domain_select_at_the_candidate_boundary(D, K_):
+    """D non-zero counts just below, at and above the 2048 candidate
+    keys the select sorts in LDS: with one key more a radix pass runs
+    first (4097: more than twice the buffer)."""
+    rng = np.random.default_rng(D * 3 + K_)
+    keys = _keys(D, rng)
+    want = _select(_boundary_rows(D, rng), keys, K_)
+    assert want[0, :, 0].view(np.uint32).tolist() == keys[:K_].tolist()
+    assert (want[0, :, 1] == 5).all()
+    assert want[1, :, 1].tolist() == list(range(D, D - K_, -1))
+    assert (want[:, :, 1] > 0).all()
+    assert (want[:, :-1, 1] >= want[:, 1:, 1]).all()
 
 
 def test_domain_select_among_thousands_of_ties():
