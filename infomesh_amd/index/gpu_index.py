@@ -26,6 +26,7 @@ docs per GPU; the bench uses the BASELINE 10M-doc/8-GPU config.
 from __future__ import annotations
 
 import math
+import os
 import re
 from dataclasses import dataclass
 
@@ -207,8 +208,17 @@ class GpuShard:
         self._collapse_ws: dict[str, torch.Tensor] = {}
         self._topk = None
         self._topk_dense = None
-        self._topk_pruned = None    # dense selector over block maxima
+        # selectors over block maxima, one per plane (the planes may run
+        # on two streams, and a wide shard gives each a workspace)
+        self._topk_pruned = None
+        self._topk_pruned_bm25 = None
         self._dense_bmax: dict = {}  # [B, NB] block maxima, per B
+        # BM25 plane from block maxima (bm25_block(bmax=) + TopKPruned,
+        # W = 64) on unmasked batches of a shard whose segments all start
+        # at a multiple of 64; off (also INFOMESH_BM25_PRUNED=0, for
+        # measuring the two apart) = always the fused histogram + TopK
+        self.bm25_pruned = os.environ.get("INFOMESH_BM25_PRUNED") != "0"
+        self._bm25_bmax: dict = {}   # [B, ceil(N/64)] block maxima, per B
         self._dense_graphs: dict = {}
         # hipGraph-capture the dense plane; set by the overlapped query
         # plane, off for direct search() callers
@@ -531,6 +541,7 @@ class GpuShard:
         self._dense_graphs = {}
         self._dense_bufs = {}
         self._dense_bmax = {}
+        self._bm25_bmax = {}
         self._bm25_hists = {}
         self._live_bits = None
         # n_docs or the row order changed (a delete alone sets a dead
@@ -1025,18 +1036,32 @@ class GpuShard:
         np.cumsum(np.bincount(qrows, minlength=B), out=qt_off[1:])
         bd = self._pick_bd(B)
         U = len(uterms)
-        # fused topk pass 1: the block kernel histograms every score it
-        # writes, so the top-k select skips one full read of the [B, N]
-        # array (~0.9 ms/batch at 10M docs)
-        hists = getattr(self, "_bm25_hists", None)
-        if hists is None:
-            hists = self._bm25_hists = {}
-        hist = hists.get(B)
-        if hist is None:
-            hist = hists[B] = torch.zeros(
-                B * 256, device=dev, dtype=torch.int32)
-        else:
-            hist.zero_()
+        # Unmasked batch, every segment starting at a multiple of 64 (a
+        # 64-column block then lies in one segment): the block kernel
+        # also writes each block's maximum and the select reads those
+        # and k blocks per row, never [B, N]. A mask would have to keep
+        # failing documents out of the maxima.
+        pruned = (mask is None and self.bm25_pruned and dev.type == "cuda"
+                  and all(s.doc_base % 64 == 0 for s in self.segments))
+        bmax = hist = None
+        if pruned:
+            bmax = self._bm25_bmax.get(B)
+            if bmax is None or bmax.shape != (B, (N + 63) // 64):
+                bmax = self._bm25_bmax[B] = torch.empty(
+                    B, (N + 63) // 64, device=dev, dtype=torch.float32)
+        elif mask is None:
+            # fused topk pass 1: the block kernel histograms every score
+            # it writes, so the top-k select skips one full read of the
+            # [B, N] array (~0.9 ms/batch at 10M docs)
+            hists = getattr(self, "_bm25_hists", None)
+            if hists is None:
+                hists = self._bm25_hists = {}
+            hist = hists.get(B)
+            if hist is None:
+                hist = hists[B] = torch.zeros(
+                    B * 256, device=dev, dtype=torch.int32)
+            else:
+                hist.zero_()
         tp = mark("shard.chunks", tp)
         # don't overwrite the pinned staging buffers while a prior
         # step's async H2D copy could still be in flight
@@ -1055,7 +1080,7 @@ class GpuShard:
                 self._h2d(f"qe{si}", seg.h_offs[uterms + 1], torch.int64),
                 bounds, scores, seg.doc_base, seg.n_docs, bd,
                 self.avgdl, k1=BM25_K1, b=BM25_B,
-                hist1=hist if mask is None else None)
+                hist1=hist, bmax=bmax)
         if dev.type == "cuda":
             if evt is None:
                 evt = self._h2d_evt = torch.cuda.Event()
@@ -1083,7 +1108,11 @@ class GpuShard:
             dom_top = K.domain_select(cnt, dom_keys, TOP_FETCH + 1)
             tally = DomainTally(cnt, dom_keys)
             tp = mark("shard.topdomains", tp)
-        if mask is None:
+        if pruned:
+            if self._topk_pruned_bm25 is None:
+                self._topk_pruned_bm25 = K.TopKPruned(dev)
+            out = self._topk_pruned_bm25(scores, bmax, 64, k)
+        elif mask is None:
             out = topk(scores, k, ext_hist1=hist)
         else:
             out = topk(scores, k, mask=mask[0], row_pred=mask[1])

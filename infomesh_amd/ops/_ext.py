@@ -62,6 +62,11 @@ _SIGNATURES: dict[str, list] = {
                             c_void_p, c_void_p, c_int, c_int, c_long,
                             c_long, c_long, c_int, c_float, c_float,
                             c_float, c_void_p],
+    "infomesh_bm25_block_bmax": [c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_int, c_long,
+                                 c_long, c_long, c_int, c_float, c_float,
+                                 c_float, c_void_p],
     "infomesh_score_combine": [c_void_p, c_void_p, c_void_p, c_float,
                                c_float, c_long, c_void_p],
     "infomesh_simhash_fingerprint": [c_void_p, c_void_p, c_void_p, c_long,
@@ -113,7 +118,6 @@ _SIGNATURES: dict[str, list] = {
     "infomesh_topk_pruned": [c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                              c_void_p, c_int, c_long, c_int, c_void_p],
     "infomesh_topk_pruned_workspace_u32": [c_int, c_long, c_int, c_int],
-    "infomesh_topk_pruned_zero_u32": [c_int],
     "infomesh_facet_counts": [c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_long, c_void_p, c_int, c_int,
@@ -162,8 +166,8 @@ _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
              "infomesh_facet_width": c_int,
              "infomesh_facet_slot": c_int,
              "infomesh_topk_zero_u32": c_long,
+             "infomesh_topk_pruned": c_int,
              "infomesh_topk_pruned_workspace_u32": c_long,
-             "infomesh_topk_pruned_zero_u32": c_long,
              "infomesh_term_block_docs": c_int,
              "infomesh_gemm_bmax_width": c_int,
              "infomesh_gemm_bf16_nt_bmax": c_int,
@@ -174,6 +178,20 @@ _RESTYPES = {"infomesh_topk_workspace_u32": c_long,
              "infomesh_embed_layernorm": c_int}
 
 
+def bind(so: Path | str, strict: bool = True) -> ctypes.CDLL:
+    """Load a build of the extension and type its entry points.
+    strict=False skips the ones that build lacks: the probes under
+    scripts/ time an older build beside the current one."""
+    lib = ctypes.CDLL(str(so))
+    for name, argtypes in _SIGNATURES.items():
+        if not strict and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = _RESTYPES.get(name)
+    return lib
+
+
 def _try_load() -> ctypes.CDLL | None:
     global _LOAD_ERROR
     so = Path(__file__).resolve().parent / "libinfomesh_hip.so"
@@ -181,14 +199,10 @@ def _try_load() -> ctypes.CDLL | None:
         _LOAD_ERROR = f"{so} not built"
         return None
     try:
-        lib = ctypes.CDLL(str(so))
+        lib = bind(so)
     except OSError as e:
         _LOAD_ERROR = str(e)
         return None
-    for name, argtypes in _SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name)
     import os
     if os.environ.get("INFOMESH_SYNC_DEBUG"):
         return _SyncDebugLib(lib)

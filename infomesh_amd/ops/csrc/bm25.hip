@@ -25,6 +25,7 @@
 // what makes O(new) segment appends exact: BM25 stats shift with the
 // corpus while installed segments stay immutable.
 #include "common.h"
+#include "gemm_common.h"   // group_max_u32
 
 namespace {
 
@@ -69,7 +70,20 @@ __global__ __launch_bounds__(256) void bm25_bounds_kernel(
 // ~0.9 ms/batch of HBM streaming. Counts are exact (each column is
 // written and histogrammed exactly once across segments x blocks), so
 // downstream select/compact semantics are bit-identical.
-template <bool HIST>
+//
+// BMAX (instead of HIST, never both): the maximum of every 64 written
+// columns goes to bmax[q][(doc_base + d0 + c) / 64], row stride
+// ceil(rowN / 64), for infomesh_topk_pruned (W = 64), which then reads
+// the maxima and 64 * K scores per row and never streams [B, rowN]. In
+// the writeout loop a wave's 64 lanes hold exactly one such block per
+// iteration (doc_base, BD and the 256-column step are multiples of 64),
+// so the maximum is one wave reduction: DPP inside the 16-lane rows, the
+// four row results through scalar registers. Scores are sums of
+// non-negative terms, >= +0.0, so the unsigned maximum of their bit
+// patterns is their maximum and a lane past the tile contributes 0. The
+// caller guarantees doc_base % 64 == 0 and BD % 64 == 0; the last block
+// of a segment covers its valid columns only.
+template <bool HIST, bool BMAX = false>
 __global__ __launch_bounds__(256) void bm25_block_kernel(
     const int* __restrict__ doc_ids,        // [P] segment-local, asc per term
     const unsigned int* __restrict__ tfdl,  // [P] tf | dl<<16
@@ -80,6 +94,7 @@ __global__ __launch_bounds__(256) void bm25_block_kernel(
     const int* __restrict__ bounds,         // [U * nblocks * 2]
     float* __restrict__ scores,             // [B, rowN]
     unsigned* __restrict__ hist1,           // [B * 256] or null
+    float* __restrict__ bmax,               // [B, ceil(rowN / 64)] or null
     long rowN, long doc_base, long nseg, int BD, int nblocks,
     float norm_a, float norm_b, float k1p1) {
   extern __shared__ float lds_scores[];     // [BD] (+ hist copies)
@@ -128,6 +143,30 @@ __global__ __launch_bounds__(256) void bm25_block_kernel(
   // pass — nontemporal keeps them out of L2, which the posting reads
   // (shared across adjacent same-block workgroups) actually want
   float* __restrict__ srow = scores + (long)q * rowN + doc_base + d0;
+  if (BMAX) {
+    float* __restrict__ brow =
+        bmax + (long)q * ((rowN + WAVE - 1) / WAVE) + (doc_base + d0) / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    // uniform trip count: every lane takes part in the reduction
+    for (int base = 0; base < nd; base += blockDim.x) {
+      const int i = base + threadIdx.x;
+      unsigned bits = 0;
+      if (i < nd) {
+        const float v = lds_scores[i];
+        __builtin_nontemporal_store(v, srow + i);
+        bits = __float_as_uint(v);
+      }
+      bits = group_max_u32<16>(bits);
+      const unsigned m = max(
+          max((unsigned)__builtin_amdgcn_readlane((int)bits, 0),
+              (unsigned)__builtin_amdgcn_readlane((int)bits, 16)),
+          max((unsigned)__builtin_amdgcn_readlane((int)bits, 32),
+              (unsigned)__builtin_amdgcn_readlane((int)bits, 48)));
+      // the wave's block has a valid column iff its first one is valid
+      if (lane == 0 && i < nd) brow[i / WAVE] = __uint_as_float(m);
+    }
+    return;
+  }
   if (!HIST) {
     for (int i = threadIdx.x; i < nd; i += blockDim.x)
       __builtin_nontemporal_store(lds_scores[i], srow + i);
@@ -164,11 +203,13 @@ __global__ void combine_kernel(const float* __restrict__ a,
 
 }  // namespace
 
-extern "C" void infomesh_bm25_block(
+// The bounds pre-pass and one form of the block kernel: BMAX with bmax,
+// else HIST with hist1, else the plain writeout.
+static void bm25_launch(
     const void* doc_ids, const void* tfdl, const void* qt_off,
     const void* qt_ut, const void* qt_idf, const void* u_begin,
     const void* u_end, void* bounds, void* scores, void* hist1,
-    int B, int U, long rowN, long doc_base, long nseg,
+    void* bmax, int B, int U, long rowN, long doc_base, long nseg,
     int BD, float norm_a, float norm_b, float k1p1, void* stream) {
   if (nseg <= 0 || B <= 0) return;
   auto s = reinterpret_cast<hipStream_t>(stream);
@@ -183,13 +224,22 @@ extern "C" void infomesh_bm25_block(
   dim3 grid((unsigned)B, (unsigned)nblocks);
   const size_t shm = (size_t)BD * sizeof(float)
       + (hist1 ? HIST8_U32 * sizeof(unsigned) : 0);
-  if (hist1)
+  if (bmax)
+    hipLaunchKernelGGL((bm25_block_kernel<false, true>), grid, dim3(256),
+                       (size_t)BD * sizeof(float), s,
+                       (const int*)doc_ids, (const unsigned int*)tfdl,
+                       (const int*)qt_off, (const int*)qt_ut,
+                       (const float*)qt_idf, (const long*)u_begin,
+                       (const int*)bounds, (float*)scores, nullptr,
+                       (float*)bmax, rowN, doc_base, nseg, BD, nblocks,
+                       norm_a, norm_b, k1p1);
+  else if (hist1)
     hipLaunchKernelGGL(bm25_block_kernel<true>, grid, dim3(256), shm, s,
                        (const int*)doc_ids, (const unsigned int*)tfdl,
                        (const int*)qt_off, (const int*)qt_ut,
                        (const float*)qt_idf, (const long*)u_begin,
                        (const int*)bounds, (float*)scores,
-                       (unsigned*)hist1,
+                       (unsigned*)hist1, nullptr,
                        rowN, doc_base, nseg, BD, nblocks,
                        norm_a, norm_b, k1p1);
   else
@@ -197,9 +247,34 @@ extern "C" void infomesh_bm25_block(
                        (const int*)doc_ids, (const unsigned int*)tfdl,
                        (const int*)qt_off, (const int*)qt_ut,
                        (const float*)qt_idf, (const long*)u_begin,
-                       (const int*)bounds, (float*)scores, nullptr,
+                       (const int*)bounds, (float*)scores, nullptr, nullptr,
                        rowN, doc_base, nseg, BD, nblocks,
                        norm_a, norm_b, k1p1);
+}
+
+extern "C" void infomesh_bm25_block(
+    const void* doc_ids, const void* tfdl, const void* qt_off,
+    const void* qt_ut, const void* qt_idf, const void* u_begin,
+    const void* u_end, void* bounds, void* scores, void* hist1,
+    int B, int U, long rowN, long doc_base, long nseg,
+    int BD, float norm_a, float norm_b, float k1p1, void* stream) {
+  bm25_launch(doc_ids, tfdl, qt_off, qt_ut, qt_idf, u_begin, u_end, bounds,
+              scores, hist1, nullptr, B, U, rowN, doc_base, nseg, BD, norm_a,
+              norm_b, k1p1, stream);
+}
+
+// infomesh_bm25_block that writes block maxima instead of a histogram:
+// bmax [B, ceil(rowN / 64)] f32, non-null; doc_base % 64 == 0 and
+// BD % 64 == 0 (see BMAX above bm25_block_kernel).
+extern "C" void infomesh_bm25_block_bmax(
+    const void* doc_ids, const void* tfdl, const void* qt_off,
+    const void* qt_ut, const void* qt_idf, const void* u_begin,
+    const void* u_end, void* bounds, void* scores, void* bmax,
+    int B, int U, long rowN, long doc_base, long nseg,
+    int BD, float norm_a, float norm_b, float k1p1, void* stream) {
+  bm25_launch(doc_ids, tfdl, qt_off, qt_ut, qt_idf, u_begin, u_end, bounds,
+              scores, nullptr, bmax, B, U, rowN, doc_base, nseg, BD, norm_a,
+              norm_b, k1p1, stream);
 }
 
 extern "C" void infomesh_score_combine(const void* a, const void* b,

@@ -40,12 +40,16 @@
 //
 // Pruned variant (infomesh_topk_pruned, at the end of the file): for a
 // producer that also wrote the maximum of every block of W consecutive
-// columns. The K blocks with the largest maxima hold the top K, so the
-// passes above run over the [B, NB] maxima and then over K gathered
-// blocks per row, never over [B, N]: 19.5k + 6.4k elements per row at
-// 1.25M columns, W = 64, K = 100, instead of 3 x 1.25M. Same contract.
+// columns. The K blocks with the largest maxima hold the top K, so one
+// kernel, one workgroup per row, selects over the NB maxima and then over
+// the K chosen blocks, never over [B, N]: 19.5k + 6.4k elements per row
+// at 1.25M columns, W = 64, K = 100, instead of 3 x 1.25M. Its contract
+// is stronger: ties at rank K go to the lowest columns. The steps, the
+// contract and the argument for it stand above infomesh_topk_pruned.
 // At 128 rows (device events, 7 rounds of 10 uncaptured calls, median):
-// 372 -> 137 us at 1.25M columns, 2612 -> 163 us at 10M.
+// streaming 372 us, the earlier sixteen-launch composition 130 us, this
+// kernel 38 us at 1.25M columns; 2612 / 151 / 69 us at 10M
+// (docs/performance.md).
 #include "common.h"
 
 #define TOPK_CAP 8192
@@ -427,84 +431,322 @@ unsigned long long* cand_of(unsigned* ws, long B) {
 }
 
 // ---- pruned select from block maxima (infomesh_topk_pruned) ------------
-// gather_blocks_kernel, one workgroup per row: sort the row's K1 chosen
-// block ids ascending (then position order in the gathered row IS global
-// index order, which the tie rule needs), keep them in blk, and copy the
-// K1 blocks of W scores side by side into gath [B, K1 * W]. Columns >= N
-// of the row's last block take the bit pattern below: its ordered key is
-// 0, under -inf's, so no real score ever loses its place to padding.
-#define PRUNE_THREADS 1024
-#define PRUNE_PAD 0xffffffffu
-__global__ __launch_bounds__(PRUNE_THREADS) void gather_blocks_kernel(
-    const float* __restrict__ scores, const int* __restrict__ ids,
-    int* __restrict__ blk, float* __restrict__ gath, long N, long NB,
-    int W, int K1) {
-  __shared__ int d[1024];
-  const int b = blockIdx.x;
-  int n2 = 64;
-  while (n2 < K1) n2 <<= 1;
-  for (int i = threadIdx.x; i < n2; i += blockDim.x)
-    d[i] = i < K1 ? ids[(long)b * K1 + i] : 0x7fffffff;
-  __syncthreads();
-  for (int k = 2; k <= n2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < n2; i += blockDim.x) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const bool up = ((i & k) == 0);
-          const int a = d[i], c = d[ixj];
-          if ((a > c) == up) { d[i] = c; d[ixj] = a; }
+// row_select_kernel, one workgroup of ROW_THREADS per row, everything in
+// LDS, no global workspace. The steps are the ones listed above
+// infomesh_topk_pruned; the pieces they share:
+//
+// Keys. Both levels rank by row_key: float_to_ordered with -0.0 folded
+// onto +0.0, so the two zeros tie (and order by column) already in the
+// selection, not only in the emitted order. A block maximum taken in
+// float_to_ordered order maps to the maximum of its scores' keys, the
+// fold being monotone. Key 0 is below -inf's and marks the columns >= N
+// of the row's last block: no real score loses its place to padding.
+//
+// ROW_STAGE keys of LDS hold the row of maxima while the blocks are
+// chosen, then the chosen blocks' scores. Scores that do not fit
+// (K = 1024 at W = 64) are read from global memory in every pass.
+// Maxima that do not fit (past 1.57M columns at W = 64) get one more
+// level instead, because six passes of one workgroup over a 625 KB row
+// measured 381 us at 128 x 10M: group_max_kernel, grid-wide, writes the
+// maximum of every G consecutive block maxima (G = ceil(NB / ROW_STAGE))
+// to the workspace, the row kernel chooses K1 of those groups by the same
+// rule and then K1 blocks among their K1 * G children. That is the
+// contract of this very selector applied to the maxima as scores with
+// block width G, so the K1 blocks are the ones the direct choice takes.
+// K1 * G must fit the stage too: G <= ROW_GROUP_MAX, 37.7M columns at
+// W = 64.
+#define ROW_THREADS 1024
+#define ROW_WAVES (ROW_THREADS / WAVE)
+#define ROW_STAGE 24576
+// Keys a thread loads before it uses the first: a level read from global
+// memory by one workgroup lives on the loads it keeps in flight.
+#define ROW_U_LDS 4
+#define ROW_U_MEM 16
+#define ROW_GROUP_MAX (ROW_STAGE / 1024)
+
+DEVINL unsigned row_key(float f) {
+  const unsigned o = float_to_ordered(f);
+  return o == 0x7fffffffu ? 0x80000000u : o;   // -0.0 -> +0.0
+}
+
+struct RowLds {
+  unsigned stage[ROW_STAGE];       // staged keys of the current level
+  unsigned hist[HIST8_U32];        // padded histogram copies (common.h)
+  unsigned bins[256];              // the copies summed
+  unsigned wave_gt[ROW_WAVES], wave_eq[ROW_WAVES];
+  unsigned sel_bin, sel_cum;
+  int blk[1024];                   // chosen block ids, ascending
+  int grp[1024];                   // chosen groups of G blocks, ascending
+  unsigned long long sort[1024];   // survivors: ~key << 32 | column
+};
+
+// This lane's rank among the set bits of a wave ballot.
+DEVINL unsigned lane_rank(unsigned long long m) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32),
+                                   __builtin_amdgcn_mbcnt_lo((unsigned)m, 0));
+}
+
+// The Kth largest of key_at(0 .. n-1), all 32 bits of it, one byte per
+// pass from the top: histogram the byte among the keys that match the
+// prefix so far, then wave 0 scans the 256 bins from the top (4 bins a
+// lane, a shuffle prefix sum across lanes) for the bin where the running
+// count reaches K. Returns the key; `above` is the count strictly above
+// it. With fewer than K keys every pass falls through to bin 0, as
+// select_bin does. All threads of the workgroup call it.
+template <int U, typename KeyAt>
+DEVINL unsigned row_radix_select(RowLds& l, long n, unsigned K,
+                                 unsigned& above, KeyAt key_at) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  unsigned prefix = 0, cum = 0;
+  for (int sh = 24; sh >= 0; sh -= 8) {
+    hist8_zero(l.hist);
+    __syncthreads();
+    unsigned* my = hist8_mine(l.hist);
+    for (long base = threadIdx.x; base < n; base += ROW_THREADS * U) {
+      unsigned o[U];   // all U loads in flight before the first use
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long i = base + (long)u * ROW_THREADS;
+        o[u] = i < n ? key_at(i) : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        // (o >> sh >> 8): the bytes above this one; sh + 8 may be 32
+        if (base + (long)u * ROW_THREADS < n &&
+            (sh == 24 || (o[u] >> sh >> 8) == prefix))
+          atomicAdd(&my[(o[u] >> sh) & 255], 1u);
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 256) {
+      unsigned sum = 0;
+#pragma unroll
+      for (int c = 0; c < HIST8_COPIES; ++c)
+        sum += l.hist[c * HIST8_STRIDE + threadIdx.x];
+      l.bins[threadIdx.x] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x < WAVE) {
+      // lane L owns bins 255 - 4L .. 252 - 4L, highest first
+      unsigned c[4], tot = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        c[j] = l.bins[255 - 4 * lane - j];
+        tot += c[j];
+      }
+      unsigned inc = tot;   // inclusive prefix sum over lanes
+#pragma unroll
+      for (int off = 1; off < WAVE; off <<= 1) {
+        const unsigned v = __shfl_up(inc, off, WAVE);
+        if (lane >= off) inc += v;
+      }
+      unsigned run = cum + inc - tot;   // count above this lane's bins
+      int hit = -1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (hit < 0) {
+          if (run + c[j] >= K) hit = j; else run += c[j];
         }
+      }
+      const unsigned long long found = __ballot(hit >= 0);
+      if (found == 0) {
+        // never reaches K: bin 0, everything above it counted
+        if (lane == WAVE - 1) { l.sel_bin = 0; l.sel_cum = run - c[3]; }
+      } else if (lane == __ffsll((long long)found) - 1) {
+        l.sel_bin = 255 - 4 * lane - hit;
+        l.sel_cum = run;
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | l.sel_bin;
+    cum = l.sel_cum;
+  }
+  above = cum;
+  return prefix;
+}
+
+// Ordered compaction: of key_at(0 .. n-1), every key > t and the first
+// `need_eq` keys == t, in ascending i. take(i, key, pos) runs once for
+// each, pos being its rank among the taken, so positions ascend with i.
+// Wave w owns one contiguous range and walks it 64 keys at a time, ranks
+// from ballots: once to count, then, after a prefix over the waves, to
+// place. A racing counter would give neither the first ties nor the
+// order. All threads of the workgroup call it.
+template <int U, typename KeyAt, typename Take>
+DEVINL void row_ordered_take(RowLds& l, long n, unsigned t, unsigned need_eq,
+                             KeyAt key_at, Take take) {
+  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+  const long per =   // keys per wave, a multiple of 64
+      ((n + ROW_WAVES - 1) / ROW_WAVES + WAVE - 1) & ~(long)(WAVE - 1);
+  const long lo = min(w * per, n), hi = min(lo + per, n);
+  unsigned ng = 0, ne = 0;
+  for (long base = lo; base < hi; base += WAVE * U) {
+    unsigned o[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = base + u * WAVE + lane;
+      o[u] = i < hi ? key_at(i) : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool in = base + u * WAVE + lane < hi;
+      ng += __popcll(__ballot(in && o[u] > t));
+      ne += __popcll(__ballot(in && o[u] == t));
+    }
+  }
+  if (lane == 0) { l.wave_gt[w] = ng; l.wave_eq[w] = ne; }
+  __syncthreads();
+  unsigned og = 0, oe = 0;   // taken / tied keys before this wave's range
+  for (int v = 0; v < w; ++v) { og += l.wave_gt[v]; oe += l.wave_eq[v]; }
+  for (long base = lo; base < hi; base += WAVE * U) {
+    unsigned o[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = base + u * WAVE + lane;
+      o[u] = i < hi ? key_at(i) : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = base + u * WAVE + lane;
+      const bool gt = i < hi && o[u] > t, eq = i < hi && o[u] == t;
+      const unsigned long long mg = __ballot(gt), me = __ballot(eq);
+      const unsigned rg = og + lane_rank(mg), re = oe + lane_rank(me);
+      if (gt || (eq && re < need_eq)) take(i, o[u], rg + min(re, need_eq));
+      og += __popcll(mg);
+      oe += __popcll(me);
+    }
+  }
+  __syncthreads();
+}
+
+// gmax[b][j] = the maximum, in row_key order, of bmax[b][j*G .. j*G+G-1]
+// (the blocks < NB of the last group).
+__global__ __launch_bounds__(256) void group_max_kernel(
+    const float* __restrict__ bmax, float* __restrict__ gmax, long NB,
+    long NG, int G) {
+  const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= NG) return;
+  const float* __restrict__ mrow = bmax + (long)blockIdx.y * NB;
+  unsigned m = 0;
+  for (long i = j * G; i < min(j * G + G, NB); ++i)
+    m = max(m, row_key(mrow[i]));
+  gmax[(long)blockIdx.y * NG + j] = ordered_to_float(m);
+}
+
+// gmax, NG, G: the group maxima, their count per row and the group size
+// when NB > ROW_STAGE; otherwise G = 1 and they are not read.
+__global__ __launch_bounds__(ROW_THREADS) void row_select_kernel(
+    const float* __restrict__ scores, const float* __restrict__ bmax,
+    const float* __restrict__ gmax, float* __restrict__ out_vals,
+    int* __restrict__ out_idx, long N, long NB, long NG, unsigned G,
+    unsigned W, int K1, int K) {
+  __shared__ RowLds l;
+  const int b = blockIdx.x;
+  const float* __restrict__ mrow = bmax + (long)b * NB;
+  const float* __restrict__ row = scores + (long)b * N;
+
+  // 1. threshold of the maxima and the K1 blocks, ids ascending.
+  // A row without NaN fills blk[0 .. K1); whatever a row fills, every
+  // entry is a block of the row.
+  for (int i = threadIdx.x; i < 1024; i += ROW_THREADS) l.blk[i] = 0;
+  unsigned above, t;
+  auto take_block = [&](long i, unsigned, unsigned pos) {
+    if (pos < (unsigned)K1) l.blk[pos] = (int)i;   // always: memory bound
+  };
+  auto key_at = [&](long i) { return l.stage[i]; };
+  if (G == 1) {   // host: NB <= ROW_STAGE
+    for (long i = threadIdx.x; i < NB; i += ROW_THREADS)
+      l.stage[i] = row_key(mrow[i]);
+    t = row_radix_select<ROW_U_LDS>(l, NB, (unsigned)K1, above, key_at);
+    row_ordered_take<ROW_U_LDS>(l, NB, t, (unsigned)K1 - above, key_at,
+                                take_block);
+  } else {        // host: NG <= ROW_STAGE, G <= ROW_GROUP_MAX
+    const float* __restrict__ grow = gmax + (long)b * NG;
+    const unsigned KG = (unsigned)min((long)K1, NG);
+    for (int i = threadIdx.x; i < 1024; i += ROW_THREADS) l.grp[i] = 0;
+    for (long i = threadIdx.x; i < NG; i += ROW_THREADS)
+      l.stage[i] = row_key(grow[i]);
+    t = row_radix_select<ROW_U_LDS>(l, NG, KG, above, key_at);
+    row_ordered_take<ROW_U_LDS>(
+        l, NG, t, KG - above, key_at, [&](long i, unsigned, unsigned pos) {
+          if (pos < KG) l.grp[pos] = (int)i;
+        });
+    // the chosen groups' blocks, in id order; key 0 past the row's end
+    const unsigned n1 = KG * G;
+    auto blk_of = [&](unsigned e) { return (long)l.grp[e / G] * G + e % G; };
+    for (unsigned e = threadIdx.x; e < n1; e += ROW_THREADS) {
+      const long id = blk_of(e);
+      l.stage[e] = id < NB ? row_key(mrow[id]) : 0u;
+    }
+    t = row_radix_select<ROW_U_LDS>(l, n1, (unsigned)K1, above, key_at);
+    row_ordered_take<ROW_U_LDS>(
+        l, n1, t, (unsigned)K1 - above, key_at,
+        [&](long e, unsigned, unsigned pos) {
+          const long id = blk_of((unsigned)e);
+          if (pos < (unsigned)K1 && id < NB) l.blk[pos] = (int)id;
+        });
+  }
+
+  // 2. threshold of the chosen blocks' scores and the survivors.
+  // Position e of the K1 * W scores is column blk[e / W] * W + e % W;
+  // the ids ascend, so e ascends with the column.
+  const unsigned n2 = (unsigned)K1 * W;
+  auto col_of = [&](unsigned e) { return (long)l.blk[e / W] * W + e % W; };
+  auto take_score = [&](long e, unsigned o, unsigned pos) {
+    const long col = col_of((unsigned)e);
+    // a padding column is taken only where N < K; it is emitted as the
+    // -inf / -1 every position past the survivors gets
+    if (pos < (unsigned)K && col < N)
+      l.sort[pos] = ((unsigned long long)(~o) << 32) | (unsigned)col;
+  };
+  for (int i = threadIdx.x; i < 1024; i += ROW_THREADS) l.sort[i] = ~0ULL;
+  unsigned T;
+  if (n2 <= ROW_STAGE) {
+    for (unsigned e = threadIdx.x; e < n2; e += ROW_THREADS) {
+      const long col = col_of(e);
+      l.stage[e] = col < N ? row_key(row[col]) : 0u;
+    }
+    T = row_radix_select<ROW_U_LDS>(l, n2, (unsigned)K, above, key_at);
+    row_ordered_take<ROW_U_LDS>(l, n2, T, (unsigned)K - above, key_at,
+                                take_score);
+  } else {
+    auto mem_key_at = [&](long e) {
+      const long col = col_of((unsigned)e);
+      return col < N ? row_key(row[col]) : 0u;
+    };
+    T = row_radix_select<ROW_U_MEM>(l, n2, (unsigned)K, above, mem_key_at);
+    row_ordered_take<ROW_U_MEM>(l, n2, T, (unsigned)K - above, mem_key_at,
+                                take_score);
+  }
+
+  // 3. sort the survivors by (value descending, column ascending): the
+  // empty slots hold the largest key and sort behind them
+  int ns = 64;
+  while (ns < K) ns <<= 1;
+  for (int k = 2; k <= ns; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const int i = threadIdx.x, ixj = i ^ j;
+      if (i < ns && ixj > i) {
+        const bool up = ((i & k) == 0);
+        const unsigned long long a = l.sort[i], c = l.sort[ixj];
+        if ((a > c) == up) { l.sort[i] = c; l.sort[ixj] = a; }
       }
       __syncthreads();
     }
   }
-  for (int i = threadIdx.x; i < K1; i += blockDim.x)
-    blk[(long)b * K1 + i] = d[i];
-  const float* row = scores + (long)b * N;
-  float* grow = gath + (long)b * K1 * W;
-  for (int e = threadIdx.x; e < K1 * W; e += blockDim.x) {
-    const long id = d[e / W];
-    const long col = id * W + e % W;
-    // id is a block of the row by construction (K1 <= NB, so the first
-    // select pads nothing); the range check is the memory-safety bound
-    grow[e] = (id >= 0 && id < NB && col < N) ? row[col]
-                                              : __uint_as_float(PRUNE_PAD);
+  for (int i = threadIdx.x; i < K; i += ROW_THREADS) {
+    const unsigned long long v = l.sort[i];
+    const bool real = v != ~0ULL;
+    out_vals[(long)b * K + i] =
+        real ? ordered_to_float(~(unsigned)(v >> 32)) : -INFINITY;
+    out_idx[(long)b * K + i] = real ? (int)(v & 0xffffffffu) : -1;
   }
 }
 
-// Positions in the gathered row -> global columns. A padding column
-// (reached only when N < K) becomes the contract's -inf / -1.
-__global__ __launch_bounds__(256) void remap_blocks_kernel(
-    const int* __restrict__ blk, float* __restrict__ out_vals,
-    int* __restrict__ out_idx, long N, int W, int K1, int K) {
-  const int b = blockIdx.x;
-  for (int i = threadIdx.x; i < K; i += blockDim.x) {
-    const int p = out_idx[(long)b * K + i];
-    if (p < 0) continue;
-    const long col = (long)blk[(long)b * K1 + p / W] * W + p % W;
-    if (col < N) {
-      out_idx[(long)b * K + i] = (int)col;
-    } else {
-      out_vals[(long)b * K + i] = -INFINITY;
-      out_idx[(long)b * K + i] = -1;
-    }
-  }
+// Blocks per group of group_max_kernel: 1 = the maxima fit the stage.
+long row_group(long NB) {
+  return NB <= ROW_STAGE ? 1 : (NB + ROW_STAGE - 1) / ROW_STAGE;
 }
-
-// Workspace of infomesh_topk_pruned, offsets in u32 units: the zeroed
-// prefixes of its two selects first (one fill covers both), then the
-// candidate buffer they share (the second select starts after the first
-// has emitted), the first select's output and the gathered scores.
-struct PrunedLayout {
-  long K1, zero2, cand, vals1, idx1, blk, gath, total;
-  PrunedLayout(long B, long NB, long K, long W)
-      : K1(K < NB ? K : NB), zero2(TopkLayout(B).cand), cand(2 * zero2),
-        vals1(cand + B * TOPK_CAP * 2), idx1(vals1 + B * K1),
-        blk(idx1 + B * K1),
-        gath((blk + B * K1 + 3) & ~3L),   // float4 reads: 16-byte aligned
-        total(gath + B * K1 * W) {}
-};
 
 }  // namespace
 
@@ -579,51 +821,77 @@ extern "C" void infomesh_topk_masked(const void* scores, void* workspace,
                     MaskRef{(const unsigned*)bits, (const int*)row_pred, W});
 }
 
-// Workspace length, and the prefix to zero before each call, of
-// infomesh_topk_pruned. W > 0.
-extern "C" long infomesh_topk_pruned_workspace_u32(int B, long N, int K,
-                                                   int W) {
-  return PrunedLayout(B, (N + W - 1) / W, K, W).total;
-}
-extern "C" long infomesh_topk_pruned_zero_u32(int B) {
-  return 2 * TopkLayout(B).cand;
+// Top-k for a producer that also wrote bmax [B, NB = ceil(N / W)], the
+// maximum of every block of W consecutive columns of a row (valid
+// columns only in the last block), taken in float_to_ordered order
+// (gemm.hip's BMAX tiles, bm25.hip's BMAX writeout). One launch of
+// row_select_kernel, one workgroup per row; it reads NB maxima and
+// K1 * W scores per row, never [B, N]. 1 <= K <= 1024, K * W < 2^31.
+// No fill, and no workspace up to ROW_STAGE block maxima per row; past
+// that group_max_kernel runs first and writes the workspace (see above
+// row_select_kernel). Returns 0, or 1 with nothing launched when the row
+// has more than ROW_GROUP_MAX * ROW_STAGE blocks.
+//
+// Per row, K1 = min(K, NB):
+//   1. t = the K1-th largest maximum (row_radix_select, 32 bits).
+//   2. Take every block whose maximum is > t and, of the blocks whose
+//      maximum equals t, the lowest ids until K1 are taken
+//      (row_ordered_take: the ids come out ascending).
+//   3. T = the Kth largest of the K1 * W scores of those blocks, columns
+//      >= N ranking below -inf.
+//   4. Keep every score > T and, of the scores equal to T, the lowest
+//      columns until K are kept.
+//   5. Sort the K survivors by (value descending, column ascending) and
+//      emit values and global columns; -inf / -1 past the N-th.
+//
+// Contract: for every row without NaN the output is exactly the first K
+// of a stable descending sort of the row, -0.0 counting as equal to
+// +0.0 (and emitted as +0.0). Stronger than infomesh_topk's, which
+// leaves open which of several equal values at rank K it returns.
+//
+// Why taking blocks this way gives it. At least K1 blocks have a maximum
+// >= t, each holding a score >= t, so (K1 = K; the case K1 = NB takes
+// every block) T >= t. Fewer than K1 blocks have a maximum > t.
+//   - A score > T >= t lies in a block whose maximum is > t: taken.
+//   - If T > t, so does a score equal to T.
+//   - If T = t, a block left out has maximum t and a higher id than every
+//     taken block with maximum t. Each of those holds a score equal to T
+//     at a lower column than anything in the block left out, and there
+//     are K - (blocks with maximum > t) of them, while at most
+//     K - (scores > T) <= K - (blocks with maximum > t) scores equal to
+//     T are needed. So the lowest-column ties needed all lie in taken
+//     blocks, and nothing in a block left out is among them.
+// Hence steps 3-5 over the taken blocks see every element of the stable
+// top K, and select exactly those.
+//
+// A row with NaN: no promise about the result; the kernel still ends
+// and stays in bounds (every LDS and output position is range-checked,
+// columns are checked against N).
+extern "C" int infomesh_topk_pruned(const void* scores, const void* bmax,
+                                    int W, void* workspace, void* out_vals,
+                                    void* out_idx, int B, long N, int K,
+                                    void* stream) {
+  if (B <= 0) return 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const long NB = (N + W - 1) / W;
+  const int K1 = (int)(K < NB ? K : NB);
+  const long G = row_group(NB), NG = (NB + G - 1) / G;
+  if (G > ROW_GROUP_MAX) return 1;
+  if (G > 1)
+    hipLaunchKernelGGL(group_max_kernel, dim3((unsigned)((NG + 255) / 256), B),
+                       dim3(256), 0, s, (const float*)bmax, (float*)workspace,
+                       NB, NG, (int)G);
+  hipLaunchKernelGGL(row_select_kernel, dim3(B), dim3(ROW_THREADS), 0, s,
+                     (const float*)scores, (const float*)bmax,
+                     (const float*)workspace, (float*)out_vals, (int*)out_idx,
+                     N, NB, NG, (unsigned)G, (unsigned)W, K1, K);
+  return 0;
 }
 
-// infomesh_topk (same output contract) for a producer that also wrote
-// bmax [B, NB = ceil(N / W)], the maximum of every block of W
-// consecutive columns of a row (valid columns only in the last block),
-// taken in float_to_ordered order (gemm.hip's BMAX tiles).
-//
-// Why it is exact: let t be a row's Kth largest block maximum. At least
-// K scores are >= t (one per block), every score > t sits in a block
-// whose maximum is > t, and fewer than K blocks have one. So the top K
-// of the union of ANY K blocks with the largest maxima has the values of
-// the true top K; scores equal to t in a block left out are
-// interchangeable at rank K, which the contract leaves open.
-//
-// Steps: select the K1 = min(K, NB) largest maxima of each row; sort
-// those block ids and gather the blocks (gather_blocks_kernel); select
-// K among the K1 * W gathered scores; map positions back to columns.
-// No pass over [B, N]: it reads NB + K1 * W scores per row.
-extern "C" void infomesh_topk_pruned(const void* scores, const void* bmax,
-                                     int W, void* workspace, void* out_vals,
-                                     void* out_idx, int B, long N, int K,
-                                     void* stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  unsigned* ws = reinterpret_cast<unsigned*>(workspace);
-  const long NB = (N + W - 1) / W;
-  const PrunedLayout L(B, NB, K, W);
-  const int K1 = (int)L.K1;
-  auto* cand = reinterpret_cast<unsigned long long*>(ws + L.cand);
-  int* idx1 = reinterpret_cast<int*>(ws + L.idx1);
-  int* blk = reinterpret_cast<int*>(ws + L.blk);
-  float* gath = reinterpret_cast<float*>(ws + L.gath);
-  topk_launch<false>(bmax, ws, cand, ws + L.vals1, idx1, B, NB, K1, nullptr,
-                     s);
-  hipLaunchKernelGGL(gather_blocks_kernel, dim3(B), dim3(PRUNE_THREADS), 0,
-                     s, (const float*)scores, idx1, blk, gath, N, NB, W, K1);
-  topk_launch<false>(gath, ws + L.zero2, cand, out_vals, out_idx, B,
-                     (long)K1 * W, K, nullptr, s);
-  hipLaunchKernelGGL(remap_blocks_kernel, dim3(B), dim3(256), 0, s, blk,
-                     (float*)out_vals, (int*)out_idx, N, W, K1, K);
+// Workspace of infomesh_topk_pruned in u32 units: the group maxima of a
+// row of more than ROW_STAGE block maxima, else nothing. Never filled.
+extern "C" long infomesh_topk_pruned_workspace_u32(int B, long N, int K,
+                                                   int W) {
+  const long NB = (N + W - 1) / W, G = row_group(NB);
+  return G > 1 ? (long)B * ((NB + G - 1) / G) : 0;
 }

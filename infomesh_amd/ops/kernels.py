@@ -413,10 +413,14 @@ class TopK:
 
 class TopKPruned:
     """TopK for scores whose producer also wrote block maxima
-    (gemm_nt_bmax): same output contract, but it reads the [B, NB]
-    maxima and k blocks of W scores per row instead of streaming
-    [B, N] three times (infomesh_topk_pruned in csrc/topk.hip). Keeps
-    its workspace like TopK; one instance per captured graph."""
+    (gemm_nt_bmax, bm25_block(bmax=)): one kernel, one workgroup per
+    row, that reads the [B, NB] maxima and k blocks of W scores per row
+    instead of streaming [B, N] three times (infomesh_topk_pruned in
+    csrc/topk.hip). No fill, and a workspace only for rows of more than
+    24 576 block maxima (grouped maxima, kept across calls; one
+    instance per captured graph). Its contract is stronger than TopK's:
+    the first k of a stable descending sort of the row, so ties at rank
+    k go to the lowest columns."""
 
     def __init__(self, device: torch.device | str = "cuda"):
         self.device = torch.device(device)
@@ -428,20 +432,21 @@ class TopKPruned:
         _check(scores, torch.float32, "scores")
         _check(bmax, torch.float32, "bmax")
         B, N = scores.shape
-        assert 1 <= k <= 1024 and W > 0
+        assert 1 <= k <= 1024 and 0 < W <= 1 << 20
         assert bmax.shape == (B, (N + W - 1) // W), \
             f"bmax must be [B, ceil(N/W)], got {tuple(bmax.shape)}"
-        lib = _ext.lib()
-        nu32 = lib.infomesh_topk_pruned_workspace_u32(B, N, k, W)
-        if self._ws is None or self._ws.numel() < nu32:
-            self._ws = torch.empty(nu32, device=scores.device,
-                                   dtype=torch.int32)
-        self._ws[:lib.infomesh_topk_pruned_zero_u32(B)].zero_()
         vals = torch.empty((B, k), device=scores.device, dtype=torch.float32)
         idx = torch.empty((B, k), device=scores.device, dtype=torch.int32)
-        lib.infomesh_topk_pruned(
-            scores.data_ptr(), bmax.data_ptr(), W, self._ws.data_ptr(),
+        lib = _ext.lib()
+        nu32 = lib.infomesh_topk_pruned_workspace_u32(B, N, k, W)
+        if nu32 and (self._ws is None or self._ws.numel() < nu32):
+            self._ws = torch.empty(nu32, device=scores.device,
+                                   dtype=torch.int32)
+        rc = lib.infomesh_topk_pruned(
+            scores.data_ptr(), bmax.data_ptr(), W,
+            self._ws.data_ptr() if nu32 else 0,
             vals.data_ptr(), idx.data_ptr(), B, N, k, _ext.stream_ptr())
+        assert rc == 0, f"topk_pruned: {N} columns at W = {W} is too wide"
         return vals, idx
 
 
@@ -921,7 +926,8 @@ def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
                scores: torch.Tensor, doc_base: int, nseg: int,
                bd: int, avgdl: float, k1: float = 1.2,
                b: float = 0.75,
-               hist1: torch.Tensor | None = None) -> torch.Tensor:
+               hist1: torch.Tensor | None = None,
+               bmax: torch.Tensor | None = None) -> torch.Tensor:
     """Doc-block LDS-accumulated BM25 for ONE posting segment.
 
     Two launches: a bounds pre-pass binary-searching each (unique term,
@@ -934,7 +940,12 @@ def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
     doc length and the current global avgdl.
 
     bounds: caller-provided i32 workspace of at least
-    U * ceil(nseg/bd) * 2 elements."""
+    U * ceil(nseg/bd) * 2 elements.
+
+    bmax (instead of hist1): [B, ceil(N/64)] f32; the kernel also writes
+    the maximum of every block of 64 columns it writes, for
+    TopKPruned(scores, bmax, 64, k). Needs doc_base % 64 == 0, so that
+    no block straddles two segments."""
     B, N = scores.shape
     U = u_begin.numel()
     nblocks = (nseg + bd - 1) // bd
@@ -949,13 +960,25 @@ def bm25_block(doc_ids: torch.Tensor, tfdl: torch.Tensor,
         # written score columns (caller zeroes it before the first
         # segment and hands it to topk(ext_hist1=...))
         assert hist1.dtype == torch.int32 and hist1.numel() >= B * 256
+    if bmax is not None:
+        assert hist1 is None, "bmax and hist1 are mutually exclusive"
+        _check(bmax, torch.float32, "bmax")
+        assert bmax.shape == (B, (N + 63) // 64), \
+            f"bmax must be [B, ceil(N/64)], got {tuple(bmax.shape)}"
+        assert doc_base % 64 == 0 and bd % 64 == 0, \
+            "bmax: segment base and doc-block must be multiples of 64"
     norm_a = k1 * (1.0 - b)
     norm_b = k1 * b / max(avgdl, 1e-9)
-    _ext.lib().infomesh_bm25_block(
+    lib = _ext.lib()
+    if bmax is not None:
+        fn, side = lib.infomesh_bm25_block_bmax, bmax.data_ptr()
+    else:
+        fn = lib.infomesh_bm25_block
+        side = 0 if hist1 is None else hist1.data_ptr()
+    fn(
         doc_ids.data_ptr(), tfdl.data_ptr(), qt_off.data_ptr(),
         qt_ut.data_ptr(), qt_idf.data_ptr(), u_begin.data_ptr(),
-        u_end.data_ptr(), bounds.data_ptr(), scores.data_ptr(),
-        0 if hist1 is None else hist1.data_ptr(),
+        u_end.data_ptr(), bounds.data_ptr(), scores.data_ptr(), side,
         B, U, N, doc_base, nseg, bd,
         norm_a, norm_b, k1 + 1.0, _ext.stream_ptr())
     return scores

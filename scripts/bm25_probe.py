@@ -5,6 +5,12 @@ BASELINE shapes. Round-1 baseline to beat: 982 us/batch kernel time at
 extra ~0.6 ms zero-fill it needed on the scores buffer.
 
 Usage (GPU box): python scripts/bm25_probe.py [--docs N] [--batch B]
+
+--compare-lib OTHER.so times search_bm25 alone, three ways alternately
+in one process: this build from block maxima, this build forced onto
+the fused histogram, and another build of the extension on the fused
+histogram (7 rounds of 10 synchronised batches each; host clock and
+device events, median [min, max] per batch).
 """
 from __future__ import annotations
 
@@ -19,6 +25,49 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 
 
+def _stats(us: list[float]) -> str:
+    us = sorted(us)
+    return f"{us[len(us) // 2]:.0f} [{us[0]:.0f}, {us[-1]:.0f}] us"
+
+
+def compare_plane(args, shard, qterms, scores) -> None:
+    from infomesh_amd.ops import _ext
+    this = _ext.lib()
+    other = _ext.bind(args.compare_lib, strict=False)
+    ways = [("this build, block maxima", this, True),
+            ("this build, histogram", this, False),
+            ("other build, histogram", other, False)]
+    host = {n: [] for n, _, _ in ways}
+    devt = {n: [] for n, _, _ in ways}
+    outs = {}
+    try:
+        for rnd in range(8):           # round 0 warms every way up
+            for name, lib, pruned in ways:
+                _ext._LIB, shard.bm25_pruned = lib, pruned
+                outs[name] = shard.search_bm25(qterms, args.k,
+                                               scores_buf=scores)
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
+                t0 = time.perf_counter()
+                e0.record()
+                for _ in range(10):
+                    shard.search_bm25(qterms, args.k, scores_buf=scores)
+                e1.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    host[name].append((time.perf_counter() - t0) * 1e5)
+                    devt[name].append(e0.elapsed_time(e1) * 100.0)
+    finally:
+        _ext._LIB, shard.bm25_pruned = this, True
+    ref = outs[ways[2][0]]
+    for name, _, _ in ways:
+        v, i = outs[name]
+        print(f"{name}: host {_stats(host[name])}, device "
+              f"{_stats(devt[name])}; values equal the other build's "
+              f"{torch.equal(v, ref[0])}, ids differ in "
+              f"{int((i != ref[1]).sum())} of {i.numel()}")
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=1_250_000)
@@ -29,6 +78,8 @@ def main() -> None:
                     help="split the corpus into this many segments")
     ap.add_argument("--bd", type=int, default=0,
                     help="override the doc-block size")
+    ap.add_argument("--compare-lib", metavar="OTHER.so",
+                    help="time search_bm25 against another build")
     args = ap.parse_args()
 
     from infomesh_amd.ops import _build
@@ -60,6 +111,10 @@ def main() -> None:
     qterms, _ = synth_queries(args.batch, n_terms=4, seed=1, device=dev)
     B, N = args.batch, args.docs
     scores = torch.empty(B, N, device=dev, dtype=torch.float32)
+
+    if args.compare_lib:
+        compare_plane(args, shard, qterms, scores)
+        return
 
     # warmup
     for _ in range(5):
